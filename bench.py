@@ -10,16 +10,24 @@ the presets' value), on-device Philox draws.  Inputs are resident in HBM before 
 value = algorithmic bytes of all ranks / time, algorithmic bytes per step = (8 + 2w)·N
 (encode reads 4N, writes wN; decode reads wN, writes 4N).
 
-The same line carries a ``topk`` object: the Top-K codec (k = 1 % per tensor, error
+With ``--full`` the same line carries a ``topk`` object: the Top-K codec (k = 1 % per tensor, error
 feedback, weighting fused) on the same arena, algorithmic bytes 16N + 24k per step
 (§8d), with its own roofline and CPU baseline.  ``--codec topk`` makes Top-K the line.
 
-  python bench.py [--gpus N --steps K --warmup W --config llama400m --bits 4]
+  python bench.py [--gpus N --steps K --warmup W --config llama400m --bits 4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles and warms up, times the K steps and prints the line (metric, value,
+ms_per_step and the workload's description).  ``--dump-outputs DIR`` also writes what the last timed
+step returned (dump_outputs).  Everything else is measured only with ``--full``: the per-kernel
+roofline figures, the ``topk`` object of the QSGD line, the other configs, the PCIe-inclusive
+rates, the PS aggregates and the CPU baselines (``--no-cpu-baseline``, ``--no-topk`` and
+``--no-extras`` drop legs of a ``--full`` run).
+
   N > 1: either the driver's torchrun (RANK/WORLD_SIZE set) or ``python bench.py --gpus N``,
   which spawns the N rank processes itself (before anything touches a GPU).
-Each rank is one synthetic client (weak scaling).  For N > 1 the PS weighted sum over
-RCCL (Σ decode(Q(w_i x_i)) / Σ w_i) and the Top-K sparse aggregate are timed after the
-codec steps and reported beside the metric.
+Each rank is one synthetic client (weak scaling).  For N > 1 ``--full`` also times the PS weighted sum over
+RCCL (Σ decode(Q(w_i x_i)) / Σ w_i) and the Top-K sparse aggregate after the
+codec steps and reports them beside the metric.
 """
 
 from __future__ import annotations
@@ -50,12 +58,17 @@ def parse():
     ap.add_argument("--ratio", type=float, default=0.01)
     ap.add_argument("--codec", choices=("qsgd", "topk"), default="qsgd")
     ap.add_argument("--chunk", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: rooflines, the topk object, other "
+                         "configs, PCIe-inclusive rates, PS aggregates, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32/float64; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-topk", action="store_true", help="skip the Top-K object of the QSGD line")
     ap.add_argument("--no-extras", action="store_true", help="skip PCIe-inclusive and PS timings")
     ap.add_argument("--dist", action="store_true",
-                    help="N = 1 in a one-rank RCCL group: also runs the PS weighted-sum / Top-K aggregate leg "
-                         "(the N > 1 code path; no scaling is implied)")
+                    help="N = 1 in a one-rank RCCL group: --full also runs the PS weighted-sum / Top-K aggregate "
+                         "leg (the N > 1 code path; no scaling is implied)")
     return ap.parse_args()
 
 
@@ -305,6 +318,43 @@ def event_ms(torch, st, fn, reps):
     return float(a.elapsed_time(b)) / reps
 
 
+DUMP_SAMPLE = 1 << 22  # elements of a large output kept by --dump-outputs (16 MiB as float32)
+
+
+def sample_index(n, limit, seed):
+    """Every index below ``n`` when there are at most ``limit``, else a fixed, seeded, sorted sample of them
+    (drawn with replacement and made unique, so a little under ``limit``)."""
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=limit, dtype=np.int64))
+
+
+def sample_positions(sizes, offsets, limit=DUMP_SAMPLE):
+    """Arena positions of the elements ``--dump-outputs`` keeps of an arena-shaped output: elements of the
+    tensors only (never the alignment padding between them, which no kernel defines), all of them or
+    sample_index's sample."""
+    sizes, offsets = np.asarray(sizes, np.int64), np.asarray(offsets, np.int64)
+    starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+    e = sample_index(int(sizes.sum()), limit, 0xD0)
+    t = np.searchsorted(starts, e, side="right") - 1
+    return offsets[t] + (e - starts[t])
+
+
+def dump_outputs(torch, out_dir, arenas, lists, plan, rank=0, world=1):
+    """``--dump-outputs``: write the last timed step's outputs as ``out_dir/<name>.npy`` (``<name>.rank<r>.npy``
+    for the ranks of N > 1).  ``arenas`` (name -> tensor with one element per arena position) are written at
+    sample_positions; ``lists`` (name -> any other tensor) whole up to DUMP_SAMPLE / 4 elements, else at
+    sample_index's sample; int64 as float64 (exact), everything else as float32.  With the same arguments
+    the inputs, the draws and the samples are the same from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+    pos = torch.from_numpy(sample_positions(plan.sizes, plan.offsets))
+    for name, t in [*arenas.items(), *lists.items()]:
+        at = pos if name in arenas else torch.from_numpy(sample_index(t.numel(), DUMP_SAMPLE >> 2, 0xD1))
+        a = t.reshape(-1).index_select(0, at.to(t.device)).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.astype(np.float64 if a.dtype == np.int64 else np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -387,7 +437,16 @@ def main():
         plan.check()
         dt = timed(q_step, args.warmup, args.steps)
         plan.check()
+        if args.dump_outputs:  # what the last timed step's encode and decode returned
+            dump_outputs(torch, args.dump_outputs, {"qsgd_payload": q[:plan.arena_end], "qsgd_decoded": y},
+                         {"qsgd_norms": norms}, plan, rank, world)
         alg_bytes_step = (8 + 2 * w) * N
+        qsgd = {
+            "value": world * alg_bytes_step * args.steps / dt / 1e9, "ms_per_step": dt / args.steps * 1e3,
+            "alg_bytes_step": alg_bytes_step,
+        }
+    if qsgd is not None and args.full:
+        # the per-kernel figures: encode and decode timed apart, in loops of their own
         reps = max(args.steps, 10)
         enc_ms = event_ms(torch, st, lambda i: plan.qsgd_encode(x, s, q_out=q, norm_out=norms, alpha=weight, seed=seed,
                                                                 offset=10_000 + i), reps)
@@ -402,20 +461,16 @@ def main():
         if dom_name == "qsgd_spec_all":  # the whole bracketed encode call, timed as one unit
             dom_name = ("omf_qsgd_encode = qsgd_spec_bracket + qsgd_spec_quant + qsgd_spec_finish"
                         " (at widths <= 4 the bracket runs as qsgd_spec_quant_fb's first workgroups)")
-        qsgd = {
-            "value": world * alg_bytes_step * args.steps / dt / 1e9, "ms_per_step": dt / args.steps * 1e3,
-            "alg_bytes_step": alg_bytes_step,
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
-                         "kernel": dom_name, "algorithmic_bytes_per_launch": dom_bytes,
-                         "avg_launch_ms": round(dom_ms, 4), "encode_ms": round(enc_ms, 4),
-                         "decode_ms": round(dec_ms, 4), "encode_GBs": round(enc_bytes / enc_ms / 1e6, 1),
-                         "decode_GBs": round(dec_bytes / dec_ms / 1e6, 1)},
-        }
+        qsgd["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
+                            "kernel": dom_name, "algorithmic_bytes_per_launch": dom_bytes,
+                            "avg_launch_ms": round(dom_ms, 4), "encode_ms": round(enc_ms, 4),
+                            "decode_ms": round(dec_ms, 4), "encode_GBs": round(enc_bytes / enc_ms / 1e6, 1),
+                            "decode_GBs": round(dec_bytes / dec_ms / 1e6, 1)}
 
     # ------------------------------------------------------------ Top-K
     topk = None
-    if args.codec == "topk" or not args.no_topk:
+    if args.codec == "topk" or (args.full and not args.no_topk):
         progress("topk steps")
         ratio = args.ratio
         ks = plan.topk_ks(ratio)
@@ -439,29 +494,40 @@ def main():
 
         if args.codec == "topk":
             settled = settle(torch, t_step)
+            if args.dump_outputs:
+                # the settle runs for a wall time, so its number of error-feedback steps varies from run
+                # to run: the residual restarts from zero here, and the dumped step's history is exactly
+                # the W warm-up and K timed steps
+                res.zero_()
         for i in range(args.warmup):
             t_step(i)
         plan.topk_stats(reset=True)
         steps_t = args.steps if args.codec == "topk" else max(5, args.steps // 2)
         dtt = timed(t_step, args.warmup, steps_t)
+        if args.dump_outputs and args.codec == "topk":  # the last timed step: its selection and arena decode
+            dump_outputs(torch, args.dump_outputs, {"topk_decoded": yt}, {"topk_values": vals, "topk_indices": idx},
+                         plan, rank, world)
         alg_t = 16 * N + 24 * K
-        reps = max(steps_t, 5)
-        tenc = event_ms(torch, st, t_enc, reps)
-        tdec = event_ms(torch, st, lambda i: plan.topk_decode_arena(vals, idx, ratio, y=yt, mode=0), reps)
-        enc_alg = 12 * N + 12 * K  # read x, read+write the residual, write values+indices
-        ach = enc_alg / (tenc * 1e-3) / 1e9
-        t_traffic, t_tsrc = pmc_traffic("topk_encode_all", args.config, s)  # every launch of one encode call
         topk = {"metric": METRIC_TOPK, "value": round(world * alg_t * steps_t / dtt / 1e9, 2), "unit": "GB/s",
                 "ms_per_step": round(dtt / steps_t * 1e3, 4), "steps": steps_t, "ratio": ratio, "k_total": K,
                 "algorithmic_bytes_per_step_per_client": alg_t,
-                "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": t_traffic, "traffic_source": t_tsrc,
-                             "kernel": "omf_topk_encode (all launches of one call; stream-asynchronous, no host wait)",
-                             "algorithmic_bytes_per_launch": enc_alg, "avg_launch_ms": round(tenc, 4),
-                             "decode_ms": round(tdec, 4)},
                 "encoder_paths": plan.topk_stats(),  # timed calls: bucket-sort fast path vs fallbacks
                 "tie_order": "index"}
-        if not args.no_extras:
+        if args.full:
+            reps = max(steps_t, 5)
+            tenc = event_ms(torch, st, t_enc, reps)
+            tdec = event_ms(torch, st, lambda i: plan.topk_decode_arena(vals, idx, ratio, y=yt, mode=0), reps)
+            enc_alg = 12 * N + 12 * K  # read x, read+write the residual, write values+indices
+            ach = enc_alg / (tenc * 1e-3) / 1e9
+            t_traffic, t_tsrc = pmc_traffic("topk_encode_all", args.config, s)  # every launch of one encode call
+            topk["roofline"] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": t_traffic, "traffic_source": t_tsrc,
+                                "kernel": "omf_topk_encode (all launches of one call; stream-asynchronous, "
+                                          "no host wait)",
+                                "algorithmic_bytes_per_launch": enc_alg, "avg_launch_ms": round(tenc, 4),
+                                "decode_ms": round(tdec, 4)}
+            topk["encoder_paths"] = plan.topk_stats()  # the event-timed encode calls included
+        if args.full and not args.no_extras:
             # the drop-in's default order (the reference's bytes where magnitudes tie): the device encode,
             # then omf_topk_torch_order's census and host rewrite of the tied tensors; wall clock
             progress("topk torch order")
@@ -479,7 +545,8 @@ def main():
         del res, yt, xs
 
     extras = {}
-    if not args.no_extras and world == 1 and qsgd is not None and args.config == "llama400m":
+    extra_legs = args.full and not args.no_extras
+    if extra_legs and world == 1 and qsgd is not None and args.config == "llama400m":
         # the other QSGD configs of BASELINE.json on one GPU: ResNet-18 at "8 levels" (s = 3, int8)
         # and the base default s = 8 (int32 wire), Llama-150M at the presets' s = 4
         progress("other configs")
@@ -507,7 +574,7 @@ def main():
                                            "algorithmic_GBs": round((8 + 2 * w_) * n_ / to / 1e9, 1)}
             del xo, qo, no, yo
         extras["other_configs"] = others
-    if not args.no_extras and world == 1 and qsgd is not None:
+    if extra_legs and world == 1 and qsgd is not None:
         progress("pcie-inclusive rate")
         # PCIe-inclusive rate: host fp32 in -> device encode -> host payload; host payload -> decode -> host fp32
         xh = torch.empty(plan.arena_end, dtype=torch.float32, pin_memory=True)
@@ -579,7 +646,7 @@ def main():
                                     "pipelined": "uplink and downlink on two streams, step i's downlink beside step "
                                                  "i+1's uplink (PCIe full duplex); steady state over 8 steps"}
         del xh, qh, yh, xd, q2, n2, qd, nd
-    if not args.no_extras and dist.is_initialized():
+    if extra_legs and dist.is_initialized():
         progress("PS aggregates over the process group")
         from omnifed_amd.ps import GpuOps, qsgd_weighted_round, topk_sparse_aggregate, total_weight
 
@@ -611,16 +678,16 @@ def main():
             extras["topk_sparse_aggregate"] = agg
 
     cpu = cpu_t = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if qsgd is not None:
             cpu = cpu_baseline(torch, named, s)
         if topk is not None:
             cpu_t = cpu_baseline_topk(torch, named, args.ratio)
-    if topk is not None:
+    if topk is not None and args.full:
         topk["cpu_baseline"] = cpu_t
 
     if rank == 0:
-        common = {"n_gpus": world, "warmup": args.warmup,
+        common = {"n_gpus": world, "warmup": args.warmup, "full": args.full,
                   "settle": {"seconds": SETTLE_S, "untimed_steps": settled,
                              "why": "GPU clock ramp from idle (bench.settle); before the W warm-up steps"},
                   "higher_is_better": True, "scaling": "weak",
@@ -635,8 +702,8 @@ def main():
                                "tensors": len(sizes), "elements_per_client": N, "bit_width": s,
                                "algorithmic_bytes_per_step_per_client": qsgd["alg_bytes_step"],
                                "fp32_gradient_GBs": round(qsgd["value"] * 4 / (8 + 2 * w), 2),
-                               "parallelism": f"clients{world}"},
-                    "roofline": qsgd["roofline"], "cpu_baseline": cpu, "topk": topk, **extras}
+                               "parallelism": f"clients{world}"}}
+            measured = {"roofline": qsgd.get("roofline"), "cpu_baseline": cpu, "topk": topk}
         else:
             line = {"metric": METRIC_TOPK, "value": topk["value"], "unit": "GB/s", "steps": topk["steps"],
                     "ms_per_step": topk["ms_per_step"], **common,
@@ -644,8 +711,10 @@ def main():
                                            f"client weighting fused, arena decode, one client per GPU",
                                "tensors": len(sizes), "elements_per_client": N, "k_total": topk["k_total"],
                                "algorithmic_bytes_per_step_per_client": topk["algorithmic_bytes_per_step_per_client"],
-                               "parallelism": f"clients{world}"},
-                    "roofline": topk["roofline"], "cpu_baseline": cpu_t, **extras}
+                               "parallelism": f"clients{world}"}}
+            measured = {"roofline": topk.get("roofline"), "cpu_baseline": cpu_t}
+        if args.full:  # what only --full measures
+            line.update(measured, **extras)
         print(json.dumps(line), file=line_out, flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

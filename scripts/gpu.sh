@@ -48,7 +48,7 @@ case "$task" in
     shift || true
     rm -rf gpurun_out/${T}_prof
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/${T}_prof" -o run \
-      -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-extras "$@" \
+      -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras "$@" \
       > gpurun_out/${T}_prof.log 2>&1 || { tail -20 gpurun_out/${T}_prof.log; exit 2; }
     s=$(find gpurun_out/${T}_prof -name '*kernel_stats.csv' | head -n 1)
     [ -n "$s" ] && cp "$s" gpurun_out/${T}_kernel_stats.csv && cat gpurun_out/${T}_kernel_stats.csv
@@ -59,7 +59,7 @@ case "$task" in
     for c in FETCH_SIZE WRITE_SIZE; do
       rm -rf gpurun_out/${T}_pmc_$c
       timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$R/gpurun_out/${T}_pmc_$c" -o run \
-        -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-extras "$@" \
+        -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras "$@" \
         > gpurun_out/${T}_pmc_$c.log 2>&1 || { tail -20 gpurun_out/${T}_pmc_$c.log; exit 2; }
     done
     python3 scripts/pmc_traffic.py gpurun_out/${T}_pmc_FETCH_SIZE gpurun_out/${T}_pmc_WRITE_SIZE \
@@ -72,7 +72,7 @@ case "$task" in
     # the decoder); SQ_PROG=topk over the Llama-400M Top-K encode + decode (bench.py --codec topk)
     T=${1:-r04_r18}
     if [ "${SQ_PROG:-r18}" = topk ]; then
-      PROG=("$R/bench.py" --codec topk --steps 5 --warmup 2 --no-cpu-baseline --no-extras); CFG=llama400m
+      PROG=("$R/bench.py" --full --codec topk --steps 5 --warmup 2 --no-cpu-baseline --no-extras); CFG=llama400m
     else
       PROG=("$R/scripts/exp/r18_ab.py" 3 1); CFG=resnet18
     fi
@@ -105,8 +105,8 @@ case "$task" in
     cp gpurun_out/${T}_s4_pmc_traffic.json gpurun_out/${T}_s8_pmc_traffic.json
     PMC_BITS=8 bash scripts/gpu.sh pmc ${T} --bits 8 --no-topk || exit 4
     cp gpurun_out/${T}_s8_pmc_traffic.json profiles/pmc_traffic.json
-    bash scripts/gpu.sh bench ${T} || exit 5
-    bash scripts/gpu.sh bench ${T}_s8 --bits 8 --no-topk --no-cpu-baseline || exit 5
+    bash scripts/gpu.sh bench ${T} --full || exit 5
+    bash scripts/gpu.sh bench ${T}_s8 --full --bits 8 --no-topk --no-cpu-baseline || exit 5
     cp gpurun_out/${T}_s8_bench.json profiles/${T}_s8_bench.json
     bash scripts/gpu.sh wire ${T} > /dev/null || exit 6
     cp gpurun_out/${T}_kernel_stats.csv profiles/${T}_kernel_stats.csv

@@ -68,3 +68,41 @@ def test_settle_runs_untimed_steps_for_its_wall_time():
     assert n == len(calls) >= 10
     assert min(calls) >= 10_000_000
     assert syncs[0] == 0 and syncs[-1] == n  # before the first step and after the last
+
+
+def test_sample_positions_skips_padding_and_is_fixed():
+    """--dump-outputs: the kept arena positions are tensor elements only (no alignment padding),
+    sorted, all of them under the limit and the same seeded sample from call to call over it."""
+    import numpy as np
+
+    sizes, offsets = [7, 100, 65], [0, 64, 192]
+    allpos = bench.sample_positions(sizes, offsets)
+    want = np.concatenate([np.arange(o, o + n) for o, n in zip(offsets, sizes)])
+    assert allpos.dtype == np.int64 and np.array_equal(allpos, want)
+    some = bench.sample_positions(sizes, offsets, limit=40)
+    assert 0 < len(some) <= 40 and np.all(np.diff(some) > 0)
+    assert set(some.tolist()) <= set(want.tolist())
+    assert np.array_equal(some, bench.sample_positions(sizes, offsets, limit=40))
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: arena-shaped outputs at the tensors' positions, lists whole, int64 as float64
+    and everything else as float32, one .npy per name."""
+    import numpy as np
+    import torch
+
+    class _Plan:
+        sizes, offsets = [3, 2], [0, 64]
+
+    q = torch.arange(66, dtype=torch.int8)
+    y = torch.arange(66, dtype=torch.float32) * 0.5
+    idx = torch.tensor([5, 2**40 + 1], dtype=torch.int64)
+    bench.dump_outputs(torch, str(tmp_path / "out"), {"q": q, "y": y}, {"norms": y[:2], "idx": idx}, _Plan)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["idx", "norms", "q", "y"]
+    assert got["q"].dtype == np.float32 and got["q"].tolist() == [0, 1, 2, 64, 65]
+    assert got["y"].dtype == np.float32 and got["y"].tolist() == [0, 0.5, 1, 32, 32.5]
+    assert got["norms"].dtype == np.float32 and got["norms"].tolist() == [0, 0.5]
+    assert got["idx"].dtype == np.float64 and got["idx"].tolist() == [5, 2**40 + 1]
+    bench.dump_outputs(torch, str(tmp_path / "out"), {"q": q}, {}, _Plan, rank=1, world=2)
+    assert os.path.exists(tmp_path / "out" / "q.rank1.npy")
