@@ -78,9 +78,47 @@ struct DeviceGuard {
 
 // ---------------------------------------------------------------- device helpers
 
+// One dword of every lane moved by a DPP control that reads no lane out of range (all rows and banks
+// written; bound_ctrl set, so the destination needs no initial value).
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov_f64(double v) {
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return __longlong_as_double((long long)(((uint64_t)dpp_mov<CTRL>((uint32_t)(b >> 32)) << 32) | dpp_mov<CTRL>((uint32_t)b)));
+}
+
+// Butterfly sum of a full wave, result in every lane: v += v[lane ^ o] for o = 32, 16, 8, 4, 2, 1 (the
+// fp64 bits depend on this pairing tree; every strategy's norm is built on it).  No LDS traffic:
+//   o = 32, 16  v_permlane32_swap / v_permlane16_swap of v with itself leave {own half | partner half}
+//               in the two results, whose sum is v + v[lane ^ o] in both halves (+ commutes exactly);
+//   o = 8       DPP row_ror:8;
+//   o = 4       lane ^ 7 (DPP row_half_mirror) then lane ^ 3 (quad_perm [3,2,1,0]);
+//   o = 2, 1    DPP quad_perm [2,3,0,1] / [1,0,3,2].
+// Every lane of the wave must be active (each call site is wave-uniform).
 __device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+    const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    v = __longlong_as_double((long long)(((uint64_t)h[0] << 32) | l[0])) +
+        __longlong_as_double((long long)(((uint64_t)h[1] << 32) | l[1]));
+  }
+  {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v = __longlong_as_double((long long)(((uint64_t)h[0] << 32) | l[0])) +
+        __longlong_as_double((long long)(((uint64_t)h[1] << 32) | l[1]));
+  }
+  v += dpp_mov_f64<0x128>(v);                      // row_ror:8
+  v += dpp_mov_f64<0x1B>(dpp_mov_f64<0x141>(v));   // row_half_mirror, then quad_perm [3,2,1,0]
+  v += dpp_mov_f64<0x4E>(v);                       // quad_perm [2,3,0,1]
+  v += dpp_mov_f64<0xB1>(v);                       // quad_perm [1,0,3,2]
   return v;
 }
 
@@ -135,9 +173,13 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
 __device__ __forceinline__ float u24(uint32_t w) { return (float)(w & 0xFFFFFFu) * 5.9604644775390625e-08f; }
 
 // Four 24-bit uniforms from three consecutive 32-bit words (96 bits, little-endian fields).
+// The two fields that straddle a word are one byte permute each (v_perm_b32: selector bytes 0-3 take
+// the second operand's bytes, 4-7 the first's, 0x0c is a zero byte): shift and mask in one instruction.
 __device__ __forceinline__ float4 u24x4(uint32_t w0, uint32_t w1, uint32_t w2) {
-  return make_float4(u24(w0), u24(__builtin_amdgcn_alignbit(w1, w0, 24)), u24(__builtin_amdgcn_alignbit(w2, w1, 16)),
-                     (float)(w2 >> 8) * 5.9604644775390625e-08f);
+  constexpr float k = 5.9604644775390625e-08f;
+  return make_float4(u24(w0), (float)__builtin_amdgcn_perm(w1, w0, 0x0c050403u) * k,  // {w0.b3, w1.b0, w1.b1, 0}
+                     (float)__builtin_amdgcn_perm(w2, w1, 0x0c040302u) * k,           // {w1.b2, w1.b3, w2.b0, 0}
+                     (float)(w2 >> 8) * k);
 }
 
 // Correctly rounded x / d from r = RN(1/d): Markstein's theorem (one Newton step brings

@@ -779,14 +779,20 @@ __global__ __launch_bounds__(kBrThreads) __attribute__((amdgpu_waves_per_eu(8)))
 // raised to 2^-26 in the lower product only (x / n may underflow to 0 where |x| c does not:
 // such an element is left undecided); a decided level needs no clamp (ceil(dl) <= the exact
 // level <= L); NaN gives kl != kh.  scripts/exp/spec_check.c checks this exact form.
-__device__ __forceinline__ void spec_quad(float4 x, float4 u, float c_lo, float c_hi, int32_t (&q)[4], bool& und) {
+// und collects the wave's lane mask of undecided quads: each compare writes its mask to scalar
+// registers and the four are or-ed there (a per-lane flag costs a select and a second compare to
+// turn into the mask); a caller that has dead lanes masks them out.
+__device__ __forceinline__ float raise_u(float u) {  // max(u, 2^-26) of a draw (>= +0, never NaN): an integer maximum
+  return __uint_as_float(max(__float_as_uint(u), 0x32800000u));
+}
+__device__ __forceinline__ void spec_quad(float4 x, float4 u, float c_lo, float c_hi, int32_t (&q)[4], uint64_t& und) {
   const float xs[4] = {x.x, x.y, x.z, x.w}, us[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const float ax = fabsf(xs[c]);
-    const float kl = ceilf(fmaf(ax, c_lo, -fmaxf(us[c], 0x1p-26f)));
+    const float kl = ceilf(fmaf(ax, c_lo, -raise_u(us[c])));
     const float kh = ceilf(fmaf(ax, c_hi, -us[c]));
-    und |= kl != kh;
+    und |= __builtin_amdgcn_fcmpf(kl, kh, 14 /* une: kl != kh */);
     q[c] = (int32_t)copysignf(kh, xs[c]);
   }
 }
@@ -799,14 +805,14 @@ __device__ __forceinline__ void spec_quad(float4 x, float4 u, float c_lo, float 
 // kl == kh decides it; bf16 subnormals (|vn| < 2^-126) fall under the u == 0
 // rule as in fp32.
 __device__ __forceinline__ void spec_quad_fmt(float4 x, float4 u, float c_lo, float c_hi, float dl, int32_t (&q)[4],
-                                              bool& und) {
+                                              uint64_t& und) {
   const float xs[4] = {x.x, x.y, x.z, x.w}, us[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const float ax = fabsf(xs[c]);
-    const float kl = ceilf(fmaf(ax, c_lo, -(fmaxf(us[c], 0x1p-26f) + dl)));
+    const float kl = ceilf(fmaf(ax, c_lo, -(raise_u(us[c]) + dl)));
     const float kh = ceilf(fmaf(ax, c_hi, dl - us[c]));
-    und |= kl != kh;
+    und |= __builtin_amdgcn_fcmpf(kl, kh, 14 /* une */);
     q[c] = (int32_t)copysignf(kh, xs[c]);
   }
 }
@@ -842,7 +848,8 @@ __device__ __forceinline__ void spec_block(const SpecArgs& a, int64_t blk, int64
                                            int64_t tb, GetBr get_br, uint32_t* slot, uint64_t* part, float anorm,
                                            int tid) {
   const EncArgs& e = a.e;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: list and record bases are scalar
   float4 v[kSpecV];
   load_f4<kSpecV, FULL, true>(e.x, b, end, v, tid);  // x is read once: nontemporal (the fix uses the records)
   int4 araw[AW ? kSpecV : 1];
@@ -901,13 +908,15 @@ __device__ __forceinline__ void spec_block(const SpecArgs& a, int64_t blk, int64
       const int64_t el = b + 4 * ((int64_t)k * kThreads + tid);
       const bool live = FULL || el < end;
       int32_t qq[4];
-      bool und = false;
-      if (FMT == kFmtF32) spec_quad(v[k], uu[k], br.c_lo, br.c_hi, qq, und);
-      else spec_quad_fmt(v[k], uu[k], br.c_lo, br.c_hi, FMT == kFmtF16 ? 0x1p-25f * e.levels : 0.0f, qq, und);
+      uint64_t m = 0;  // the wave's undecided quads
+      if (FMT == kFmtF32) spec_quad(v[k], uu[k], br.c_lo, br.c_hi, qq, m);
+      else spec_quad_fmt(v[k], uu[k], br.c_lo, br.c_hi, FMT == kFmtF16 ? 0x1p-25f * e.levels : 0.0f, qq, m);
       if (live) store_quad<WIDTH>(e, el, FULL ? el + 4 : end, qq);
-      const uint64_t m = __ballot(live && und);
-      if (m) {  // rare: list this wave's undecided quads
-        const uint32_t pos = cnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (!FULL) m &= __builtin_amdgcn_ballot_w64(live);
+      if (m) {  // rare: list them
+        const bool und = (m >> lane) & 1ull;
+        const uint32_t pos =  // the listed quads of lower lanes (v_mbcnt: no lane mask built on the hot path)
+            cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (live && und && pos < (uint32_t)PW) {  // the quad, its x and its draws: no re-read
           list[pos] = (uint32_t)(el >> 2);
           float4* rec = a.recs + 2 * ((blk * kWaves + wave) * PW + pos);
@@ -2745,13 +2754,18 @@ static int encode_launch(omf_plan* p, const float* x, float alpha, int32_t s, co
     // The wide pass's one-wave workgroups reserve 10 KiB of LDS each (unused): 16 per CU, i.e. four
     // waves per SIMD — 0.556-0.559 ms per Llama-400M s = 8 encode against 0.589 uncapped, 0.565 at 12
     // KiB, 0.635 at 16 KiB (scripts/exp/occ_ab.sh, two interleaved rounds); OMF_SPEC_LDS_W overrides.
-    // The s <= 4 pass is co-bound by its VALU and keeps every wave (24 KiB: 0.367 against 0.360 ms).
+    // The s <= 4 pass lost under a cap at first (24 KiB: 0.367 against 0.360 ms); it reserves 24 KiB since
+    // its wave sum left the LDS and its quad math shed a tenth of its VALU work (below).
     static const size_t plds_w = [] { const char* v = omf::knob("OMF_SPEC_LDS_W"); return v ? (size_t)atoi(v) : (size_t)10240; }();
     if (fb) {  // the bracket folded into the pass (its first workgroups)
       const int64_t nbrw = (int64_t)kFbParts * p->n_spec_br;
       const dim3 gfb((unsigned)(nbrw + p->n_spec_blocks));
+      // The plain pass reserves 24 KiB of LDS per workgroup (unused): six workgroups per CU, where the
+      // registers would admit eight (profiles/r07_pass_schedule_ab.txt; OMF_SPEC_LDS
+      // overrides).  The fused PS step's pass, which also stores the average, is not capped (not measured).
+      static const size_t plds_n = [] { const char* v = omf::knob("OMF_SPEC_LDS"); return v ? (size_t)atoi(v) : (size_t)24576; }();
       if (div) hipLaunchKernelGGL((qsgd_spec_quant_fb<1, true>), gfb, blk, 0, st, sa, sa.br_items, nbrw, sa.begins);
-      else hipLaunchKernelGGL((qsgd_spec_quant_fb<1, false>), gfb, blk, 0, st, sa, sa.br_items, nbrw, sa.begins);
+      else hipLaunchKernelGGL((qsgd_spec_quant_fb<1, false>), gfb, blk, plds_n, st, sa, sa.br_items, nbrw, sa.begins);
     } else if (wfb) {  // wide levels: the bracket's one-wave parts first, then the pass's one-wave blocks
       const int64_t nbrw = (int64_t)kWfbParts * p->n_spec_br;
       const dim3 gw((unsigned)(nbrw + p->n_spec_blocks * kWaves)), bw(64);

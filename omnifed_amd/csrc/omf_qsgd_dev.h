@@ -140,9 +140,11 @@ __device__ __forceinline__ void qsgd_quad(float4 x, float4 u, const Divisor& dv,
   }
 }
 
+// The low bytes of four levels in one dword: two byte permutes (v_perm_b32: selector bytes 0-3 take the
+// second operand's bytes, 4-7 the first's, 0x0c a zero byte) and an or.
 __device__ __forceinline__ uint32_t pack_i8x4(const int32_t (&q)[4]) {
-  return (uint32_t)(uint8_t)q[0] | ((uint32_t)(uint8_t)q[1] << 8) | ((uint32_t)(uint8_t)q[2] << 16) |
-         ((uint32_t)(uint8_t)q[3] << 24);
+  return __builtin_amdgcn_perm((uint32_t)q[1], (uint32_t)q[0], 0x0c0c0400u) |   // {q0.b0, q1.b0, 0, 0}
+         __builtin_amdgcn_perm((uint32_t)q[3], (uint32_t)q[2], 0x04000c0cu);    // {0, 0, q2.b0, q3.b0}
 }
 
 }  // namespace omf
