@@ -3,55 +3,62 @@
 // Semantics: SURVEY.md §8a "Exact QSGD semantics", restating
 //   src/omnifed/hybrid/compression/qsgd.py:36-96 (reference, Python/torch CPU).
 //
-// Kernel map:
-//   qsgd_encode_ordered  one launch for every tensor of a client.  Work items are
-//                        taken in ticket order (an atomic counter, so a workgroup
-//                        only ever waits on items that are already running):
-//                        RESIDENT(t)  16 Ki elements held in registers: publish the
-//                                     fp64 partial sum of squares, wait for the
-//                                     tensor norm, quantise from registers — x is
-//                                     read once (tensors of <= cap/2 items);
-//                        NORM(t)      chunk partial only (large tensors, pass 1);
-//                        QUANT(t)     wait for the norm, re-read, quantise (pass 2).
-//                        The last arriver of a tensor folds its partials in fixed
-//                        order (deterministic norm) and publishes a {tag, norm}
-//                        granule that the waiters poll.
-//   qsgd_quant_sub       norm supplied by the caller: one pass, no hand-off.
-//   qsgd_decode_flat     y = (norm * q) / L, optionally accumulated (PS).
+// Kernel map (the single-read ring encoder is omf_qsgd_ring.hip).  Every encoder
+// writes the same payload bits for the same norm.
+//   qsgd_encode_ordered    ticket-ordered encoder (strategies 0 and 1, and every norms-only pass): one
+//                          launch for every tensor.  Work items are taken in ticket order (an atomic
+//                          counter, so a workgroup only waits on items that are already running):
+//                          RESIDENT(t) holds its elements in registers, publishes the fp64 partial
+//                          sum of squares, waits for the tensor norm and quantises — x read once;
+//                          NORM(t) / QUANT(t) are the two passes of a larger tensor.  The last
+//                          arriver of a tensor folds its partials in fixed order (deterministic norm)
+//                          and publishes a {tag, norm} granule that the waiters poll.
+//   qsgd_quant_sub         norms supplied by the caller: one pass over the flat items, no hand-off.
+//   bracketed single-read encoder (strategy 3; the comment above kSpecV describes the algorithm):
+//     qsgd_spec_bracket, qsgd_spec_bracket_wide
+//                          a tensor's bracket of its norm from a sample, as a launch of its own
+//                          (wide: bit widths 5-8, kBrParts workgroups per tensor);
+//     qsgd_spec_quant      the pass: partial sums, the levels the bracket decides, the undecided
+//                          quads listed (the wide-level lists: one wave per workgroup);
+//     qsgd_spec_quant_fb, qsgd_spec_quant_wfb
+//                          the pass with the bracket folded in: its first workgroups are the
+//                          bracket's parts (wfb: wide levels, one-wave workgroups);
+//     qsgd_spec_finish     the fold of the wave partials into the norm, then the fix of the listed
+//                          quads (a tensor whose norm left its bracket is requantised whole).
+//   qsgd_encode_grid       grid encoder (strategy 4, small arenas): one workgroup per CU, x held in
+//                          registers across one grid-wide barrier.
+//   qsgd_decode_arena      y = (norm * q) / L over the arena's 4 Ki blocks, optionally accumulated (PS);
+//   qsgd_decode_flat       the same per flat item with byte loads: payloads of fewer than 4 elements.
+//   div_f32_kernel         y /= d (the in-place PS step).
+//
+// Host side (the end of the file): omf_plan_create / upload_plan carve the plan's device block from
+// the tables of omf_plan_layout.cpp; encode_launch asks choose_encoder (omf_plan_layout.h) which
+// encoder serves a call and switches over five launchers (caller norms, grid, bracket, ring,
+// ordered); decode_blocks launches the decoders.  struct omf_plan is in omf_plan.h.
 //
 // HBM-bound; no MFMA (no contraction).  Coalesced 16 B/lane fp32 loads, non-temporal
 // 16 B/lane fp32 and 4 B/lane int8 payload stores.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/omf_codec.h"
 #include "../../include/omf_codec_experimental.h"
 #include "omf_common.h"
+#include "omf_plan.h"
 #include "omf_qsgd_dev.h"
 #include "omf_ring.h"
 
 using namespace omf;
+using namespace omf::plan_layout;  // the table records and layout constants (omf_plan_layout.h)
 
 namespace {
 
-constexpr int kV = 16;                                // float4 per thread per sub-chunk
-constexpr int64_t kSub = (int64_t)kV * kThreads * 4;  // 16384 elements = 64 KiB fp32
-constexpr uint64_t kWaitTicks = 2000000ull;           // 20 ms of the 100 MHz realtime clock
-
-enum : int32_t { kNorm = 0, kQuant = 1, kResident = 2 };
-
-struct Item {
-  int64_t begin, end;  // arena element range of this work item
-  int32_t tensor, kind, chunk, pad;
-};
-
-struct TensorInfo {
-  int64_t begin, n;
-  int64_t chunk;          // elements per item of this tensor
-  int32_t nchunks, pbase;
-};
+constexpr int kV = 16;  // float4 per thread per sub-chunk
+static_assert(kSub == (int64_t)kV * kThreads * 4, "a flat item is one sub-chunk of a 256-thread workgroup");
+static_assert(kBlkWaves == kWaves, "one wave partial per wave of a block's workgroup");
 
 struct EncArgs {
   const float* x;
@@ -412,7 +419,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_quant_sub(EncArgs a) {
 //                      whose sample was degenerate is requantised whole from x (the rare path).
 // Payload bits equal every other strategy's for the same norm.
 constexpr int kSpecV = 4;                                    // float4 rows per thread
-constexpr int64_t kSpecBlk = (int64_t)kSpecV * kThreads * 4;  // 4096 elements per block
+static_assert(kSpecBlk == (int64_t)kSpecV * kThreads * 4, "4096 elements per block");
 constexpr int kSpecSlot = 32;                                 // words per block: 4 waves x 7 quads (+ 4 spare)
 constexpr int kSpecPerWave = 7;                               // listed quads per wave
 // Wide levels (bit_width 5-8, fp32: the reference's default int32 wire at 8): the undecided fraction
@@ -421,47 +428,10 @@ constexpr int kSpecPerWave = 7;                               // listed quads pe
 // four fix threads share a wave slot.  Slots and records of this capacity are allocated at the
 // plan's first wide encode.
 constexpr int kSpecPerWaveWide = 32;
-constexpr int kSpecMaxBitsWide = 8;
 __host__ __device__ constexpr int spec_slot_words(int pw) { return pw == kSpecPerWave ? kSpecSlot : kWaves * pw; }
 constexpr int64_t kSpecExact = 16384;                         // tensors read whole by the bracket
-constexpr int kSpecRun = 64;                                  // elements per sampled run (256 B: DRAM-friendly)
-constexpr int kSpecRuns = 512;                                // sampled runs per larger tensor (at most)
-// wide levels: 4x the sampled elements (half the bracket width: the undecided quads, the fix pass's
-// work, grow with L and with the bracket's width) in runs of 256 elements (1 KiB: four times fewer
-// random DRAM accesses than 2 Ki runs of 64), kBrParts workgroups per tensor, 128 runs each
-constexpr int kSpecRunWide = 256;
-constexpr int kSpecRunsWide = 512;
-#ifndef OMF_BR_PARTS  // experiment builds may override it (scripts/exp/s8_variants.sh)
-#define OMF_BR_PARTS 2
-#endif
-constexpr int kBrParts = OMF_BR_PARTS;
-constexpr int kSpecSeg = 4096;                                // wave partials per fold workgroup (16 loads per thread
-                                                              // in flight: a 4 Mi-element tensor is one segment)
-// Widest level count the bracket serves: the undecided fraction grows with L (a level step is
-// norm / L wide), and at L = 32 a 1 Mi-element tensor's sampled bracket already leaves ~1.3
-// undecided quads per wave; wider payloads take the two-pass encoder.
-constexpr int kSpecMaxBits = 4;
-constexpr int kSpecMinBits = 1;  // L >= 2 (spec_check.c's underflow argument)
-
-struct SpecBracket {
-  float c_lo, c_hi, n_lo, n_hi;
-  uint32_t mode;  // 0 speculate, 1 deferred (degenerate sample: the fix pass requantises)
-  uint32_t pad[3];
-};
-
-// Bracket work item: one per tensor, one workgroup each (qsgd_spec_bracket writes the
-// tensor's bracket from that workgroup's sums alone; upload_plan builds exactly one).
-struct SpecBrItem {
-  int64_t begin, n;  // the tensor's arena range
-  int64_t base;      // stratum length n / R (R = runs of the tensor); rem = n % R strata are one longer
-  int32_t R, rem;
-  int32_t tensor, Rw;  // Rw: the runs of kSpecRunWide sampled for wide levels (strata n / Rw)
-};
-// Fold work item: wave partials [p_begin, p_end) of tensor `tensor`, segment `seg` of `nsegs`.
-struct SpecFoldItem {
-  int64_t p_begin, p_end;
-  int32_t tensor, seg, nsegs, sbase;
-};
+// (the sampled runs, the bracket parts, the fold segments and the bit widths served: omf_plan_layout.h;
+// SpecBracket: omf_plan.h)
 
 struct SpecArgs {
   EncArgs e;               // x, q, norm_out, items (flat 16 Ki items), alpha, levels, Philox key
@@ -980,7 +950,7 @@ __global__ __launch_bounds__(64 * WPB) void qsgd_spec_quant(SpecArgs a, const Sp
 // then poll their tensor's granules.  The bracket workgroups have the lowest ids, so they are
 // dispatched before any pass block and never wait; a pass block's poll is bounded anyway (20 ms and a
 // minimum of polls): on expiry the tensor is flagged and requantised whole by the finish — exact.
-constexpr int kFbParts = 8;  // 64 runs each: four float4 per thread (the pass's blocks' register budget)
+// (kFbParts = 8 parts of 64 runs each: four float4 per thread, the pass's blocks' register budget)
 
 __device__ __forceinline__ void spec_bracket_part(const SpecArgs& a, const SpecBrItem* __restrict__ items, int64_t wg) {
   __shared__ double red[kWaves];
@@ -1097,13 +1067,9 @@ __global__ __launch_bounds__(kThreads) void qsgd_spec_quant_fb(SpecArgs a, const
 // the multipliers; the pass's one-wave blocks poll them as qsgd_spec_quant_fb's do.  A bracket from
 // other partial sums than the separate launch's may list other quads: the payload is exact either
 // way (test_fused_bracket_equals_bracket_launch).
-#ifndef OMF_WFB_PARTS  // experiment builds may override them
-#define OMF_WFB_PARTS 16
-#endif
-#ifndef OMF_WFB_PASSES
+#ifndef OMF_WFB_PASSES  // experiment builds may override it (and kWfbParts, omf_plan_layout.h)
 #define OMF_WFB_PASSES 8
 #endif
-constexpr int kWfbParts = OMF_WFB_PARTS;
 constexpr int kPassesW = OMF_WFB_PASSES;
 
 __device__ __forceinline__ void spec_bracket_part_wide(const SpecArgs& a, const SpecBrItem* __restrict__ items,
@@ -1407,7 +1373,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_spec_finish(SpecArgs a, const S
 // a workgroup barrier, sc1 loads; one workgroup per CU.  The counter wait is bounded (20 ms
 // and a minimum number of polls); on expiry each workgroup recomputes the partials it needs
 // from x in the producers' exact order (same bits) and sets err bit 2.
-constexpr int kGridNB = 3;  // 4 Ki blocks per quarter-workgroup per launch
+// (kGridNB 4 Ki blocks per quarter-workgroup per launch)
 
 struct GridArgs {
   EncArgs e;                    // x, q, norm_out, alpha, fmt, levels, Philox key / offset, err, wait_ticks
@@ -1692,7 +1658,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_flat(DecArgs a) {
 // or an accumulate — measured on Llama-400M (scripts/exp/dec_shapes.hip, interleaved): int8
 // 0.298-0.304 ms against 0.331 with 4 quads, int32 0.492 against 0.550, accumulate 0.556 / 0.748
 // against 0.612 / 0.807 (fewer bytes per thread, more workgroups in flight per CU).
-constexpr int64_t kDecBlk = (int64_t)4 * kThreads * 4;  // 4096 elements per binfo table block
+static_assert(kDecBlk == (int64_t)4 * kThreads * 4, "4096 elements per binfo table block");
 template <int WIDTH, bool ACC>
 constexpr int kDecQuads = (WIDTH == 1 && !ACC) ? 2 : 1;
 
@@ -1799,471 +1765,98 @@ __global__ __launch_bounds__(kThreads) void div_f32_kernel(float* __restrict__ y
 }  // namespace
 
 // ====================================================================== host side
-
-struct omf_plan {
-  int device = 0;
-  int32_t nt = 0;
-  int64_t chunk = kSub;
-  std::vector<int64_t> sizes, offsets;
-  int64_t arena_end = 0;
-  int64_t cap = 0;               // tensors of <= cap items take the register-resident path
-  int32_t strategy = 2;          // 0 register-resident + two-pass, 1 ticket-ordered two-pass, 2 single-read ring,
-                                 // 3 bracketed single-read (default by size: omf_plan_create)
-  int32_t last_encoder = -1;     // the encoder the latest encode launched (omf_plan_last_encoder)
-  uint64_t wait_ticks = kWaitTicks;      // norm waits (ring: expiry recomputes; bracketed fix: expiry fails)
-  uint64_t lds_wait_ticks = kWaitTicks;  // the ring's on-chip hand-off waits (expiry aborts the workgroup)
-  uint32_t epoch = 0;            // last granule tag used (host-side launch counter)
-  int32_t ev = 8;                // encode rows per thread (sub-chunk = ev * 1024 elements): 8 measured
-                                 // faster than 16 for the two-pass encoder (0.596 vs 0.606 ms, Llama-400M)
-  int64_t n_enc[2] = {0, 0};
-  Item* d_enc[2] = {nullptr, nullptr};
-  TensorInfo* d_tinfo[2] = {nullptr, nullptr};
-  int64_t n_flat = 0, n_partials = 0;
-  Item* d_flat = nullptr;
-  uint64_t* d_partials = nullptr;
-  int64_t* d_sizes = nullptr;   // per-tensor element counts (Top-K)
-  int64_t* d_begins = nullptr;  // per-tensor arena offsets (Top-K)
-  void* d_block = nullptr;      // one allocation for everything above
-  uint8_t* d_sync = nullptr;    // [ticket u32, err u32, pad 8][counters u32 x nt, pad16][granules u64 x nt, pad16]
-  size_t sync_bytes = 0, off_counters = 16, off_gran = 0;
-  // single-read ("ring") encoder, strategy 2 (omf_qsgd_ring.hip)
-  int32_t ring_cfg = 0;         // omf_qsgd_ring.hip kConfigs[0]: 64 KiB chunks, 8 loader + 8 quantiser waves
-  int32_t ring_grid = 0;
-  int32_t ring_big_mode = 1;     // 0: QUANT chunks of a large tensor ring_gap items after its NORM chunks; 1: NORM first, QUANT last
-  int64_t ring_gap = -1;         // items (-1: one grid)
-  int64_t ring_hold_override = 0;  // > 0: hold limit in chunks (tests)
-  uint32_t ring_dbg = 0;           // test / experiment switches (omf_plan_set_debug), 0 in production
-  uint32_t ring_epoch = 0;
-  int64_t n_ring = 0, n_ring_gran = 0, ring_hold_max = 0, ring_two_pass = 0;
-  omf::ring::Item* d_ring = nullptr;
-  omf::ring::Tensor* d_ring_t = nullptr;
-  uint64_t* d_ring_gran = nullptr;
-  unsigned long long* d_ring_prof = nullptr;  // 16 phase counters (OMF_RING_DBG & 4)
-  // bracketed single-read encoder, strategy 3: per-tensor brackets / flags / status, per
-  // 4 Ki-element block partials and undecided-quad slots
-  int64_t n_spec_blocks = 0, n_spec_br = 0, n_spec_fold = 0;
-  SpecBrItem* d_spec_br_items = nullptr;
-  SpecFoldItem* d_spec_fold_items = nullptr;
-  uint64_t* d_spec_seg_part = nullptr;
-  uint32_t* d_spec_cnt = nullptr;  // fold_cnt x nt
-  uint32_t spec_epoch = 0;
-  uint32_t spec_skip = 0;  // test / experiment switches (omf_plan_set_debug), 0 in production
-  // The bracket's width in sigmas (OMF_SPEC_ZSIG overrides both): a tensor whose norm falls
-  // outside is requantised whole by the finish (exact; a miss per tensor at z sigmas has
-  // probability ~erfc(z / sqrt 2): 6e-5 at 4, 6e-7 at 5), and a narrower bracket lists fewer
-  // undecided quads.  scripts/exp/zsig_ab.sh, Llama-400M, two interleaved rounds: s = 4 encode
-  // 0.349-0.352 ms at 5 sigmas against 0.357-0.361 at 6 (4: 0.350); s = 8 0.546-0.547 ms at 4
-  // against 0.556-0.559 at 5 (3.5: 0.542-0.545).
-  float spec_zsig = 5.0f;
-  float spec_zsig_wide = 4.0f;
-  SpecBracket* d_spec_br = nullptr;
-  uint64_t* d_spec_ngran = nullptr;  // per tensor {epoch << 1 | bad, norm} granules of the fold
-  uint64_t* d_spec_part = nullptr;
-  uint32_t* d_spec_slots = nullptr;
-  uint32_t* d_spec_heads = nullptr;
-  float4* d_spec_recs = nullptr;  // listed quads' x and draws (32 B each)
-  uint32_t* d_spec_slots_w = nullptr;  // the wide-level capacity (kSpecPerWaveWide), made at the first
-  float4* d_spec_recs_w = nullptr;     // wide encode (bit_width 5-8)
-  double* d_spec_br_part = nullptr;    // wide: the bracket parts' partial sums and arrival counters
-  uint32_t* d_spec_br_cnt = nullptr;
-  // the fused-bracket pass (OMF_SPEC_FB=0 / omf_plan_set_fused_bracket turn it off): Llama-400M s = 4
-  // step 0.6977-0.7021 ms against 0.7009-0.7067 with the bracket's own launch (three interleaved
-  // pairs), the encode alone unchanged (0.348-0.360 both); profiles/r05_fused_bracket_ab.txt
-  int32_t spec_fb = 1;
-  double* d_spec_fb_part = nullptr;    // its parts' partial sums, arrival counters and granules
-  uint32_t* d_spec_fb_cnt = nullptr;
-  uint64_t* d_spec_brgran = nullptr;
-  int32_t spec_last_pw = kSpecPerWave;  // the list capacity of the latest bracketed encode
-  int32_t spec_wide = 1;  // wide levels (5-8 bits, fp32) through the bracket (1) or as before (0): OMF_SPEC_WIDE
-  // arena-aligned decoder: per 4 Ki block, tensor id | (1 << 31 when inside it)
-  int64_t n_dec_blocks = 0;
-  uint32_t* d_dec_binfo = nullptr;
-  uint32_t* d_spec_flags = nullptr;
-  uint32_t* d_spec_status = nullptr;
-  // grid encoder (strategy 4): one workgroup per CU, kGridNB 4 Ki blocks per quarter
-  int32_t grid_wgs = 0;             // workgroups of a launch (CUs; 0 = unavailable)
-  uint32_t* d_grid_pbeg = nullptr;  // per tensor: first flat item (one partial per item)
-  uint32_t* d_grid_pcnt = nullptr;  // per tensor: flat items
-  unsigned long long* d_grid_bar = nullptr;  // arrival counter (zeroed at upload)
-  uint64_t grid_launches = 0;
-  // Top-K tiled decode: per-ratio constant tables (omf_topk.hip), allocated on first use, with
-  // one host word each (the table's size facts)
-  struct TopkTable {
-    uint64_t key;
-    void* dev;
-    uint64_t host;
-    std::vector<int64_t> counts;  // tables keyed by explicit per-tensor counts: the exact counts
-  };
-  std::vector<TopkTable> topk_tables;
-  omf::TopkKnobs topk_knobs;
-  // Launches that use the sync block / granules are ordered across streams: a launch on a
-  // stream other than the previous one first waits for the previous launch's event.
-  hipEvent_t last_ev = nullptr;
-  hipStream_t last_stream = nullptr;
-  bool last_valid = false;
-};
-
-// Order this launch after the plan's previous stateful launch when the stream changes: the event is
-// recorded on the previous stream at the switch (it covers everything enqueued there so far, the
-// plan's launches included), not after every call — an event packet between two kernels of one
-// stream idled the GPU ~5 us per encode even without a system-scope fence (rocprofv3 kernel trace).
-// So the previous stream must still exist when the plan moves to another one (include/omf_codec.h).
-static int plan_enter(omf_plan* p, hipStream_t st) {
-  if (p->last_valid && p->last_stream != st) {
-    if (!p->last_ev) OMF_HIP(hipEventCreateWithFlags(&p->last_ev, kOrderEventFlags));
-    OMF_HIP(hipEventRecord(p->last_ev, p->last_stream));
-    OMF_HIP(hipStreamWaitEvent(st, p->last_ev, 0));
-  }
-  return OMF_OK;
-}
-static int plan_leave(omf_plan* p, hipStream_t st) {
-  p->last_stream = st;
-  p->last_valid = true;
-  return OMF_OK;
-}
-
-// Plan internals shared with omf_topk.hip.
-namespace omf_plan_access {
-const void* flat_items(const omf_plan* p, int64_t* n) {
-  *n = p->n_flat;
-  return p->d_flat;
-}
-int32_t ntensors(const omf_plan* p) { return p->nt; }
-int device(const omf_plan* p) { return p->device; }
-int64_t arena_end(const omf_plan* p) { return p->arena_end; }
-// The decoder's block table (tensor id | bit 31 = the block lies inside it) and its block size.
-const uint32_t* dec_blocks(const omf_plan* p, int64_t* n, int64_t* block_elems) {
-  *n = p->n_dec_blocks;
-  *block_elems = kDecBlk;
-  return p->d_dec_binfo;
-}
-const int64_t* d_sizes(const omf_plan* p) { return p->d_sizes; }
-const int64_t* d_begins(const omf_plan* p) { return p->d_begins; }
-const std::vector<int64_t>& sizes(const omf_plan* p) { return p->sizes; }
-// A plan-owned device buffer of `bytes` for `key` (allocated, and *fresh set, on first use;
-// not on the hot path after that), with a host word the caller keeps beside it.  nullptr if
-// the allocation fails.
-void* topk_table(omf_plan* p, uint64_t key, size_t bytes, bool* fresh, uint64_t** host) {
-  *fresh = false;
-  for (auto& e : p->topk_tables)
-    if (e.key == key) {
-      *host = &e.host;
-      return e.dev;
-    }
-  void* d = nullptr;
-  if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-  p->topk_tables.push_back({key, d, 0, {}});
-  *host = &p->topk_tables.back().host;
-  *fresh = true;
-  return d;
-}
-// The same for tables keyed by an explicit per-tensor count vector (a received Top-K message's
-// k_t): matched on the exact counts.  At most kMaxCountTables are kept; making one more frees the
-// oldest (hipFree waits for the device, so no queued launch still reads it).
-void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes, bool* fresh, uint64_t** host) {
-  constexpr uint64_t kCountsKey = 0xC0C0C0C0C0C0C0C0ull;
-  constexpr int kMaxCountTables = 8;
-  *fresh = false;
-  const size_t nt = (size_t)p->nt;
-  int held = 0;
-  for (auto& e : p->topk_tables) {
-    if (e.key != kCountsKey) continue;
-    ++held;
-    if (e.counts.size() == nt && std::equal(e.counts.begin(), e.counts.end(), counts)) {
-      *host = &e.host;
-      return e.dev;
-    }
-  }
-  if (held >= kMaxCountTables) {
-    for (auto it = p->topk_tables.begin(); it != p->topk_tables.end(); ++it)
-      if (it->key == kCountsKey) {
-        (void)hipFree(it->dev);
-        p->topk_tables.erase(it);
-        break;
-      }
-  }
-  void* d = nullptr;
-  if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-  p->topk_tables.push_back({kCountsKey, d, 0, std::vector<int64_t>(counts, counts + nt)});
-  *host = &p->topk_tables.back().host;
-  *fresh = true;
-  return d;
-}
-const std::vector<int64_t>& offsets(const omf_plan* p) { return p->offsets; }
-omf::TopkKnobs& topk_knobs(omf_plan* p) { return p->topk_knobs; }
-// The plan's device error word (omf_plan_check reports and clears it).
-uint32_t* err_word(omf_plan* p) { return reinterpret_cast<uint32_t*>(p->d_sync + 4); }
-// Stream ordering of a stateful launch outside this file (plan_enter / plan_leave).
-int order_enter(omf_plan* p, hipStream_t st) { return plan_enter(p, st); }
-int order_leave(omf_plan* p, hipStream_t st) { return plan_leave(p, st); }
-}  // namespace omf_plan_access
-
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+// struct omf_plan and its stream ordering (plan_enter / plan_leave) are in omf_plan.h; the work-item
+// tables, the carve of a device allocation and the encoder choice in omf_plan_layout.h.
 
 static bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
-// Ticket-order item sequence.  Register-resident tensors (<= cap items of kSub) are
-// emitted in place; a larger tensor emits its NORM items in place and its QUANT items
-// after the next tensor's items (one tensor of slack for the norm hand-off).
-static void build_sequence(const omf_plan& p, bool resident_ok, std::vector<Item>& seq,
-                           std::vector<TensorInfo>& tinfo, int64_t& npart) {
-  seq.clear();
-  tinfo.assign(p.nt, TensorInfo{});
-  npart = 0;
-  std::vector<Item> deferred;
-  for (int32_t t = 0; t < p.nt; ++t) {
-    const int64_t n = p.sizes[t], b = p.offsets[t];
-    const int64_t es = (int64_t)p.ev * 1024;
-    const int64_t ns = (n + es - 1) / es;
-    std::vector<Item> q_t;
-    if (ns == 1 || (resident_ok && ns <= p.cap)) {
-      tinfo[t] = TensorInfo{b, n, es, (int32_t)ns, (int32_t)npart};
-      for (int64_t c = 0; c < ns; ++c) {
-        const int64_t cb = b + c * es;
-        seq.push_back(Item{cb, std::min(b + n, cb + es), t, kResident, (int32_t)c, 0});
-      }
-      npart += ns;
-    } else {
-      const int64_t nc = (n + p.chunk - 1) / p.chunk;
-      tinfo[t] = TensorInfo{b, n, p.chunk, (int32_t)nc, (int32_t)npart};
-      for (int64_t c = 0; c < nc; ++c) {
-        const int64_t cb = b + c * p.chunk, ce = std::min(b + n, cb + p.chunk);
-        seq.push_back(Item{cb, ce, t, kNorm, (int32_t)c, 0});
-        q_t.push_back(Item{cb, ce, t, kQuant, (int32_t)c, 0});
-      }
-      npart += nc;
+// Allocates a carve's bytes into *block, binds its pointers and fills its regions.  On failure *block
+// and every pointer of the carve are NULL.
+static int make_block(const Carve& c, void** block) {
+  auto fill = [&]() -> int {
+    OMF_HIP(hipMalloc(block, c.bytes()));
+    for (const Carve::Region& r : c.regions()) {
+      void* dst = static_cast<uint8_t*>(*block) + r.offset;
+      if (!r.bytes) continue;
+      if (r.src) OMF_HIP(hipMemcpy(dst, r.src, r.bytes, hipMemcpyHostToDevice));
+      else if (r.zero) OMF_HIP(hipMemset(dst, 0, r.bytes));
     }
-    seq.insert(seq.end(), deferred.begin(), deferred.end());
-    deferred.swap(q_t);
-  }
-  seq.insert(seq.end(), deferred.begin(), deferred.end());
-}
-
-// Ring sequence: tensors of <= ring_hold_max chunks are HOLD chunks (read once);
-// larger ones are NORM chunks (partial only) plus QUANT chunks (second read), the QUANT
-// chunks placed ring_gap items later (big_mode 0) or at the very end with every NORM
-// chunk first (big_mode 1).  Items are dealt to workgroups round-robin.
-// Register-resident encoder (omf_qsgd_ring.hip qsgd_encode_rr): every single-read tensor
-// lies inside one row of `grid` consecutive items, so all its chunks are at the same
-// position of their workgroups.  Rows are packed first-fit decreasing; gaps are filled
-// with NORM items of the multi-row ("big") tensors, or with empty items when none are
-// left.  Layout: [whole rows of big NORM items][packed rows][remaining big NORM items]
-// [big QUANT items] — every NORM item precedes its tensor's QUANT items.
-static void build_rr_sequence(omf_plan& p, int64_t ch, std::vector<omf::ring::Item>& seq,
-                              std::vector<omf::ring::Tensor>& tens) {
-  namespace R = omf::ring;
-  const int64_t G = std::max<int32_t>(p.ring_grid, 1);
-  p.ring_hold_max = p.ring_hold_override > 0 ? std::min<int64_t>(G, p.ring_hold_override) : G;
-  seq.clear();
-  tens.assign(p.nt, R::Tensor{});
-  std::vector<R::Item> norm_items, quant_items;
-  std::vector<std::pair<int64_t, int32_t>> regular;  // (chunks, tensor)
-  int64_t gb = 0;
-  p.ring_two_pass = 0;
-  auto item = [&](int32_t t, int64_t k, int32_t flags) {
-    const int64_t n = p.sizes[t], b = p.offsets[t], cb = b + k * ch;
-    return R::Item{cb, std::min(b + n, cb + ch), b, n, t, flags, (int32_t)k, tens[t].nchunks, tens[t].gbase, {0, 0, 0}};
+    return OMF_OK;
   };
-  for (int32_t t = 0; t < p.nt; ++t) {
-    const int64_t nc = (p.sizes[t] + ch - 1) / ch;
-    tens[t] = R::Tensor{p.offsets[t], p.sizes[t], (int32_t)nc, (int32_t)gb, {0, 0}};
-    gb += nc;
-    if (nc <= p.ring_hold_max) {
-      regular.emplace_back(nc, t);
-    } else {
-      ++p.ring_two_pass;
-      for (int64_t k = 0; k < nc; ++k) norm_items.push_back(item(t, k, R::kPublish));
-      for (int64_t k = 0; k < nc; ++k) quant_items.push_back(item(t, k, R::kQuant));
-    }
+  const int rc = fill();
+  if (rc != OMF_OK && *block) {
+    (void)hipFree(*block);
+    *block = nullptr;
   }
-  std::stable_sort(regular.begin(), regular.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
-  std::vector<std::vector<int32_t>> rows;
-  std::vector<int64_t> room;
-  for (const auto& r : regular) {
-    size_t i = 0;
-    while (i < rows.size() && room[i] < r.first) ++i;
-    if (i == rows.size()) {
-      rows.emplace_back();
-      room.push_back(G);
-    }
-    rows[i].push_back(r.second);
-    room[i] -= r.first;
-  }
-  // Gap fillers come from the back of the NORM list; whole rows of the rest lead.
-  size_t nfill = 0;
-  for (size_t i = 0; i + 1 < rows.size(); ++i) nfill += (size_t)room[i];
-  nfill = std::min(nfill, norm_items.size());
-  const size_t avail = norm_items.size() - nfill;
-  const size_t lead = avail / (size_t)G * (size_t)G;
-  seq.insert(seq.end(), norm_items.begin(), norm_items.begin() + (ptrdiff_t)lead);
-  size_t tail = lead;                           // next NORM item not yet placed (after the lead rows)
-  size_t fill = norm_items.size() - nfill;      // next gap filler
-  for (size_t i = 0; i < rows.size(); ++i) {
-    for (int32_t t : rows[i])
-      for (int64_t k = 0; k < tens[t].nchunks; ++k) seq.push_back(item(t, k, R::kPublish | R::kQuant));
-    if (i + 1 < rows.size()) {
-      for (int64_t g = 0; g < room[i]; ++g) {
-        if (fill < norm_items.size()) seq.push_back(norm_items[fill++]);
-        else seq.push_back(R::Item{0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}});  // empty: keeps rows aligned
-      }
-    }
-  }
-  seq.insert(seq.end(), norm_items.begin() + (ptrdiff_t)tail, norm_items.begin() + (ptrdiff_t)(norm_items.size() - nfill));
-  seq.insert(seq.end(), quant_items.begin(), quant_items.end());
-  p.n_ring_gran = std::max<int64_t>(gb, 1);
+  c.bind(*block);
+  return rc;
 }
 
-static void build_ring_sequence(omf_plan& p, std::vector<omf::ring::Item>& seq,
-                                std::vector<omf::ring::Tensor>& tens) {
-  namespace R = omf::ring;
-  const R::Config c = R::config(p.ring_cfg);
-  const int64_t ch = R::chunk_elems(c);
-  if (c.kind == 1) return build_rr_sequence(p, ch, seq, tens);
-  p.ring_hold_max = p.ring_hold_override > 0 ? p.ring_hold_override : (int64_t)c.slots * p.ring_grid;
-  const int64_t gap = p.ring_gap >= 0 ? p.ring_gap : p.ring_grid;
-  seq.clear();
-  tens.assign(p.nt, R::Tensor{});
-  std::vector<R::Item> front, back;
-  std::vector<std::pair<int64_t, std::vector<R::Item>>> pending;  // (insert when seq.size() >= first, items)
-  int64_t gb = 0;
-  p.ring_two_pass = 0;
-  auto flush = [&](bool all) {
-    for (size_t i = 0; i < pending.size();) {
-      if (all || (int64_t)seq.size() >= pending[i].first) {
-        seq.insert(seq.end(), pending[i].second.begin(), pending[i].second.end());
-        pending.erase(pending.begin() + i);
-      } else {
-        ++i;
-      }
-    }
-  };
-  for (int32_t t = 0; t < p.nt; ++t) {
-    const int64_t n = p.sizes[t], b = p.offsets[t];
-    const int64_t nc = (n + ch - 1) / ch;
-    tens[t] = R::Tensor{b, n, (int32_t)nc, (int32_t)gb, {0, 0}};
-    gb += nc;
-    const bool big = nc > p.ring_hold_max;
-    std::vector<R::Item> quant;
-    for (int64_t k = 0; k < nc; ++k) {
-      const int64_t cb = b + k * ch, ce = std::min(b + n, cb + ch);
-      if (!big) {
-        seq.push_back(R::Item{cb, ce, b, n, t, R::kPublish | R::kQuant, (int32_t)k, (int32_t)nc, (int32_t)(gb - nc), {0, 0, 0}});
-        flush(false);
-      } else {
-        const R::Item norm_it{cb, ce, b, n, t, R::kPublish, (int32_t)k, (int32_t)nc, (int32_t)(gb - nc), {0, 0, 0}};
-        if (p.ring_big_mode == 1) front.push_back(norm_it);
-        else seq.push_back(norm_it);
-        quant.push_back(R::Item{cb, ce, b, n, t, R::kQuant, (int32_t)k, (int32_t)nc, (int32_t)(gb - nc), {0, 0, 0}});
-      }
-    }
-    if (big) {
-      ++p.ring_two_pass;
-      if (p.ring_big_mode == 1) back.insert(back.end(), quant.begin(), quant.end());
-      else pending.emplace_back((int64_t)seq.size() + gap, std::move(quant));
-    }
-  }
-  flush(true);
-  if (p.ring_big_mode == 1) {
-    seq.insert(seq.begin(), front.begin(), front.end());
-    seq.insert(seq.end(), back.begin(), back.end());
-  }
-  p.n_ring_gran = std::max<int64_t>(gb, 1);
-}
-
-// (Re)build both sequences and upload every table into one device allocation.
+// (Re)build every table (omf_plan_layout.cpp) and upload them into one device allocation.  Each
+// region is declared once, in the allocation's order: its pointer, element count and contents.
 static int upload_plan(omf_plan* p) {
-  std::vector<Item> seq[2], flat;
-  std::vector<TensorInfo> tinfo[2];
-  int64_t np[2];
-  build_sequence(*p, true, seq[0], tinfo[0], np[0]);
-  build_sequence(*p, false, seq[1], tinfo[1], np[1]);
-  std::vector<omf::ring::Item> rseq;
-  std::vector<omf::ring::Tensor> rtens;
-  build_ring_sequence(*p, rseq, rtens);
-  p->n_ring = (int64_t)rseq.size();
-  // Flat items (decode, norm-supplied quantise, Top-K passes): one 16 Ki sub-chunk each,
-  // the fastest decode granularity measured (profiles/r01_notes.md).
-  // Bracketed encoder tables: one bracket item per tensor (one workgroup writes its bracket)
-  // and fold segments of kSpecSeg wave partials (4 per 4 Ki block, kSub / kSpecBlk = 4 blocks
-  // per flat item).
-  std::vector<SpecBrItem> br_items;
-  std::vector<SpecFoldItem> fold_items;
-  std::vector<uint32_t> gpbeg((size_t)p->nt), gpcnt((size_t)p->nt);
-  int32_t seg_base = 0;
-  for (int32_t t = 0; t < p->nt; ++t) {
-    const int64_t n = p->sizes[t], b = p->offsets[t];
-    const int64_t p_begin = (int64_t)kWaves * 4 * (int64_t)flat.size();
-    for (int64_t c = 0; c * kSub < n; ++c) {
-      const int64_t cb = b + c * kSub;
-      flat.push_back(Item{cb, std::min(b + n, cb + kSub), t, kQuant, (int32_t)c, 0});
-    }
-    const int64_t p_end = (int64_t)kWaves * 4 * (int64_t)flat.size();
-    gpbeg[(size_t)t] = (uint32_t)(p_begin / (kWaves * 4));  // the grid encoder: one partial per item
-    gpcnt[(size_t)t] = (uint32_t)((p_end - p_begin) / (kWaves * 4));
-    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(kSpecRuns, n / (2 * kSpecRun)));
-    const int64_t Rw = std::max<int64_t>(1, std::min<int64_t>(kSpecRunsWide, n / (2 * kSpecRunWide)));
-    br_items.push_back(SpecBrItem{b, n, n / R, (int32_t)R, (int32_t)(n % R), t, (int32_t)Rw});
-    const int32_t nsegs = (int32_t)((p_end - p_begin + kSpecSeg - 1) / kSpecSeg);
-    for (int32_t q = 0; q < nsegs; ++q)
-      fold_items.push_back(SpecFoldItem{p_begin + (int64_t)q * kSpecSeg, std::min(p_end, p_begin + (int64_t)(q + 1) * kSpecSeg),
-                                        t, q, nsegs, seg_base});
-    seg_base += nsegs;
-  }
-  static_assert(kSub == 4 * kSpecBlk, "four spec blocks per flat item");
-  // decoder block table: the last tensor starting at or before the block, and whether the
-  // block lies entirely inside it
-  std::vector<uint32_t> binfo((size_t)((p->arena_end + kDecBlk - 1) / kDecBlk));
-  {
-    int32_t t = 0;
-    for (size_t k = 0; k < binfo.size(); ++k) {
-      const int64_t base = (int64_t)k * kDecBlk;
-      while (t + 1 < p->nt && p->offsets[t + 1] <= base) ++t;
-      const bool inside = p->offsets[t] <= base && base + kDecBlk <= p->offsets[t] + p->sizes[t];
-      binfo[k] = (uint32_t)t | (inside ? 0x80000000u : 0u);
-    }
-  }
-  p->n_dec_blocks = (int64_t)binfo.size();
-  p->n_spec_blocks = 4 * (int64_t)flat.size();
-  p->n_spec_br = (int64_t)br_items.size();
-  p->n_spec_fold = (int64_t)fold_items.size();
-  if ((int64_t)std::max(seq[0].size(), 4 * flat.size()) > 0x7fffffffLL) return fail(OMF_EINVAL, "too many work items");
-  p->n_enc[0] = (int64_t)seq[0].size();
-  p->n_enc[1] = (int64_t)seq[1].size();
-  p->n_flat = (int64_t)flat.size();
-  p->n_partials = std::max<int64_t>(std::max(np[0], np[1]), 1);
+  const ring::Config rc = ring::config(p->ring_cfg);
+  Desc d;
+  d.sizes = p->sizes.data();
+  d.offsets = p->offsets.data();
+  d.nt = p->nt;
+  d.chunk = p->chunk;
+  d.ev = p->ev;
+  d.cap = p->cap;
+  d.ring_chunk = ring::chunk_elems(rc);
+  d.ring_slots = rc.slots;
+  d.ring_kind = rc.kind;
+  d.ring_grid = p->ring_grid;
+  d.ring_big_mode = p->ring_big_mode;
+  d.ring_gap = p->ring_gap;
+  d.ring_hold_override = p->ring_hold_override;
+  Tables tb;
+  if (!build_tables(d, tb)) return fail(OMF_EINVAL, "too many work items");
+  p->n_enc[0] = tb.n_enc[0];
+  p->n_enc[1] = tb.n_enc[1];
+  p->n_flat = tb.n_flat;
+  p->n_partials = tb.n_partials;
+  p->n_ring = (int64_t)tb.ring.size();
+  p->n_ring_gran = tb.n_ring_gran;
+  p->ring_hold_max = tb.ring_hold_max;
+  p->ring_two_pass = tb.ring_two_pass;
+  p->n_spec_blocks = tb.n_spec_blocks;
+  p->n_spec_fold = (int64_t)tb.fold_items.size();
+  p->n_dec_blocks = (int64_t)tb.dec_binfo.size();
   p->off_counters = 16;
   p->off_gran = round16(p->off_counters + 4 * (size_t)p->nt);
   p->sync_bytes = round16(p->off_gran + 8 * (size_t)p->nt);
-  // the sync block starts the allocation (its per-call memset is 16-byte aligned and sized)
-  size_t o = round16(p->sync_bytes);
-  const size_t o_enc0 = o; o = round16(o + sizeof(Item) * seq[0].size());
-  const size_t o_enc1 = o; o = round16(o + sizeof(Item) * seq[1].size());
-  const size_t o_flat = o; o = round16(o + sizeof(Item) * flat.size());
-  const size_t o_ti0 = o; o = round16(o + sizeof(TensorInfo) * p->nt);
-  const size_t o_ti1 = o; o = round16(o + sizeof(TensorInfo) * p->nt);
-  const size_t o_part = o; o = round16(o + 8 * (size_t)p->n_partials);
-  const size_t o_sizes = o; o = round16(o + 8 * (size_t)p->nt);
-  const size_t o_begins = o; o = round16(o + 8 * (size_t)p->nt);
-  const size_t o_ring = o; o = round16(o + sizeof(omf::ring::Item) * rseq.size());
-  const size_t o_ring_t = o; o = round16(o + sizeof(omf::ring::Tensor) * rtens.size());
-  const size_t o_ring_g = o; o = round16(o + 8 * (size_t)p->n_ring_gran);
-  const size_t o_ring_p = o; o = round16(o + 8 * 16);
-  const size_t o_sp_bri = o; o = round16(o + sizeof(SpecBrItem) * br_items.size());
-  const size_t o_sp_foi = o; o = round16(o + sizeof(SpecFoldItem) * fold_items.size());
-  const size_t o_sp_segp = o; o = round16(o + 8 * fold_items.size());
-  const size_t o_sp_cnt = o; o = round16(o + 4 * (size_t)p->nt + 4);
-  const size_t o_sp_br = o; o = round16(o + sizeof(SpecBracket) * (size_t)p->nt);
-  const size_t o_sp_ngran = o; o = round16(o + 8 * (size_t)p->nt);
-  const size_t o_sp_part = o; o = round16(o + 8 * (size_t)kWaves * (size_t)p->n_spec_blocks);
-  const size_t o_sp_slots = o; o = round16(o + 4 * (size_t)kSpecSlot * (size_t)p->n_spec_blocks);
-  const size_t o_sp_heads = o; o = round16(o + 4 * (size_t)kWaves * (size_t)p->n_spec_blocks);
-  const size_t o_binfo = o; o = round16(o + 4 * binfo.size());
-  const size_t o_sp_recs = o; o = round16(o + 32 * (size_t)kWaves * kSpecPerWave * (size_t)p->n_spec_blocks);
-  const size_t o_sp_flags = o; o = round16(o + 4 * (size_t)p->nt);
-  const size_t o_sp_status = o; o = round16(o + 4 * (size_t)p->nt);
-  const size_t o_g_pbeg = o; o = round16(o + 4 * (size_t)p->nt);
-  const size_t o_g_pcnt = o; o = round16(o + 4 * (size_t)p->nt);
-  const size_t o_g_bar = o; o = round16(o + 16);
+  const size_t nt = (size_t)p->nt, nb = (size_t)p->n_spec_blocks;
+  Carve c;
+  c.zero(p->d_sync, p->sync_bytes);  // first: its per-call memset is 16-byte aligned and sized
+  c.copy(p->d_enc[0], tb.enc[0]);
+  c.copy(p->d_enc[1], tb.enc[1]);
+  c.copy(p->d_flat, tb.flat);
+  c.copy(p->d_tinfo[0], tb.tinfo[0]);
+  c.copy(p->d_tinfo[1], tb.tinfo[1]);
+  c.raw(p->d_partials, (size_t)p->n_partials);
+  c.copy(p->d_sizes, p->sizes);
+  c.copy(p->d_begins, p->offsets);
+  c.copy(p->d_ring, tb.ring);
+  c.copy(p->d_ring_t, tb.ring_t);
+  c.zero(p->d_ring_gran, (size_t)p->n_ring_gran);  // epoch 0 is never a launch's tag
+  c.zero(p->d_ring_prof, 16);
+  c.copy(p->d_spec_br_items, tb.br_items);
+  c.copy(p->d_spec_fold_items, tb.fold_items);
+  c.raw(p->d_spec_seg_part, tb.fold_items.size());
+  c.zero(p->d_spec_cnt, nt + 1);
+  c.raw(p->d_spec_br, nt);
+  c.zero(p->d_spec_ngran, nt);  // epoch 0 is never a launch's tag
+  c.raw(p->d_spec_part, kWaves * nb);
+  c.raw(p->d_spec_slots, kSpecSlot * nb);
+  c.raw(p->d_spec_heads, kWaves * nb);
+  c.copy(p->d_dec_binfo, tb.dec_binfo);
+  c.raw(p->d_spec_recs, 2 * (size_t)kWaves * kSpecPerWave * nb);
+  c.zero(p->d_spec_flags, nt);
+  c.zero(p->d_spec_status, nt);  // spec_stats reads them before any encode
+  c.copy(p->d_grid_pbeg, tb.grid_pbeg);
+  c.copy(p->d_grid_pcnt, tb.grid_pcnt);
+  c.zero(p->d_grid_bar, 2);
   DeviceGuard g(p->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   if (p->d_block) {
@@ -2271,63 +1864,59 @@ static int upload_plan(omf_plan* p) {
     (void)hipFree(p->d_block);
     p->d_block = nullptr;
   }
-  OMF_HIP(hipMalloc(&p->d_block, o));
-  uint8_t* base = static_cast<uint8_t*>(p->d_block);
-  p->d_sync = base;
-  p->d_enc[0] = reinterpret_cast<Item*>(base + o_enc0);
-  p->d_enc[1] = reinterpret_cast<Item*>(base + o_enc1);
-  p->d_flat = reinterpret_cast<Item*>(base + o_flat);
-  p->d_tinfo[0] = reinterpret_cast<TensorInfo*>(base + o_ti0);
-  p->d_tinfo[1] = reinterpret_cast<TensorInfo*>(base + o_ti1);
-  p->d_partials = reinterpret_cast<uint64_t*>(base + o_part);
-  p->d_sizes = reinterpret_cast<int64_t*>(base + o_sizes);
-  p->d_begins = reinterpret_cast<int64_t*>(base + o_begins);
-  p->d_ring = reinterpret_cast<omf::ring::Item*>(base + o_ring);
-  p->d_ring_t = reinterpret_cast<omf::ring::Tensor*>(base + o_ring_t);
-  p->d_ring_gran = reinterpret_cast<uint64_t*>(base + o_ring_g);
-  p->d_ring_prof = reinterpret_cast<unsigned long long*>(base + o_ring_p);
-  p->d_spec_br_items = reinterpret_cast<SpecBrItem*>(base + o_sp_bri);
-  p->d_spec_fold_items = reinterpret_cast<SpecFoldItem*>(base + o_sp_foi);
-  p->d_spec_seg_part = reinterpret_cast<uint64_t*>(base + o_sp_segp);
-  p->d_spec_cnt = reinterpret_cast<uint32_t*>(base + o_sp_cnt);
-  p->d_spec_br = reinterpret_cast<SpecBracket*>(base + o_sp_br);
-  p->d_spec_ngran = reinterpret_cast<uint64_t*>(base + o_sp_ngran);
-  p->d_spec_part = reinterpret_cast<uint64_t*>(base + o_sp_part);
-  p->d_spec_slots = reinterpret_cast<uint32_t*>(base + o_sp_slots);
-  p->d_spec_heads = reinterpret_cast<uint32_t*>(base + o_sp_heads);
-  p->d_dec_binfo = reinterpret_cast<uint32_t*>(base + o_binfo);
-  OMF_HIP(hipMemcpy(p->d_dec_binfo, binfo.data(), 4 * binfo.size(), hipMemcpyHostToDevice));
-  p->d_spec_recs = reinterpret_cast<float4*>(base + o_sp_recs);
-  p->d_spec_flags = reinterpret_cast<uint32_t*>(base + o_sp_flags);
-  p->d_spec_status = reinterpret_cast<uint32_t*>(base + o_sp_status);
-  p->d_grid_pbeg = reinterpret_cast<uint32_t*>(base + o_g_pbeg);
-  p->d_grid_pcnt = reinterpret_cast<uint32_t*>(base + o_g_pcnt);
-  p->d_grid_bar = reinterpret_cast<unsigned long long*>(base + o_g_bar);
-  OMF_HIP(hipMemcpy(p->d_grid_pbeg, gpbeg.data(), 4 * gpbeg.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_grid_pcnt, gpcnt.data(), 4 * gpcnt.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemset(p->d_grid_bar, 0, 16));
   p->grid_launches = 0;
-  OMF_HIP(hipMemcpy(p->d_spec_br_items, br_items.data(), sizeof(SpecBrItem) * br_items.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_spec_fold_items, fold_items.data(), sizeof(SpecFoldItem) * fold_items.size(),
-                    hipMemcpyHostToDevice));
-  OMF_HIP(hipMemset(p->d_spec_cnt, 0, 4 * (size_t)p->nt + 4));
-  OMF_HIP(hipMemset(p->d_spec_flags, 0, 4 * (size_t)p->nt));
-  OMF_HIP(hipMemset(p->d_spec_status, 0, 4 * (size_t)p->nt));  // spec_stats reads them before any encode
-  OMF_HIP(hipMemset(p->d_spec_ngran, 0, 8 * (size_t)p->nt));  // epoch 0 is never a launch's tag
-  OMF_HIP(hipMemset(p->d_ring_prof, 0, 8 * 16));
-  OMF_HIP(hipMemcpy(p->d_enc[0], seq[0].data(), sizeof(Item) * seq[0].size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_enc[1], seq[1].data(), sizeof(Item) * seq[1].size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_flat, flat.data(), sizeof(Item) * flat.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_tinfo[0], tinfo[0].data(), sizeof(TensorInfo) * p->nt, hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_tinfo[1], tinfo[1].data(), sizeof(TensorInfo) * p->nt, hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_sizes, p->sizes.data(), 8 * (size_t)p->nt, hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_begins, p->offsets.data(), 8 * (size_t)p->nt, hipMemcpyHostToDevice));
-  if (!rseq.empty())
-    OMF_HIP(hipMemcpy(p->d_ring, rseq.data(), sizeof(omf::ring::Item) * rseq.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemcpy(p->d_ring_t, rtens.data(), sizeof(omf::ring::Tensor) * rtens.size(), hipMemcpyHostToDevice));
-  OMF_HIP(hipMemset(p->d_ring_gran, 0, 8 * (size_t)p->n_ring_gran));  // epoch 0 is never a launch's tag
-  OMF_HIP(hipMemset(p->d_sync, 0, p->sync_bytes));
+  return make_block(c, &p->d_block);
+}
+
+// The buffers of a group made at the first encode that needs it: the regions declared in `c`, each
+// an allocation of its own (the fused bracket's counters and granules carved out of one allocation
+// with its sums, pages apart before, cost the Llama-400M s = 4 encode 0.342 against 0.330 ms:
+// profiles/r08_plan_host_ab.txt), zero fills on `st`.  The plan owns them (d_lazy); on failure
+// none is kept and every pointer of the group is NULL.
+static int make_buffers(omf_plan* p, const Carve& c, hipStream_t st) {
+  std::vector<void*> made;
+  auto alloc = [&]() -> int {
+    for (const Carve::Region& r : c.regions()) {
+      void* d = nullptr;
+      OMF_HIP(hipMalloc(&d, r.bytes));
+      made.push_back(d);
+      if (r.zero) OMF_HIP(hipMemsetAsync(d, 0, r.bytes, st));
+    }
+    return OMF_OK;
+  };
+  if (const int rc = alloc()) {
+    for (void* d : made) (void)hipFree(d);
+    c.bind(nullptr);
+    return rc;
+  }
+  for (size_t i = 0; i < made.size(); ++i) c.regions()[i].set(c.regions()[i].field, made[i]);
+  p->d_lazy.insert(p->d_lazy.end(), made.begin(), made.end());
   return OMF_OK;
+}
+
+// The buffers of the wide levels (bit widths 5-8), made at a plan's first wide encode: slots and
+// records of the wide list capacity, the bracket parts' partial sums and arrival counters.
+static int ensure_wide(omf_plan* p, hipStream_t st) {
+  if (p->d_spec_slots_w) return OMF_OK;
+  const size_t nt = (size_t)p->nt, nb = (size_t)p->n_spec_blocks;
+  Carve c;
+  c.raw(p->d_spec_slots_w, (size_t)spec_slot_words(kSpecPerWaveWide) * nb);
+  c.raw(p->d_spec_recs_w, 2 * (size_t)kWaves * kSpecPerWaveWide * nb);
+  c.raw(p->d_spec_br_part, 2 * (size_t)kBrParts * nt);
+  c.zero(p->d_spec_br_cnt, nt);  // left zero by every launch
+  return make_buffers(p, c, st);
+}
+
+// The fused bracket's, made at the first encode that folds the bracket into the pass: its parts'
+// partial sums, arrival counters and granules.
+static int ensure_fused_bracket(omf_plan* p, hipStream_t st) {
+  if (p->d_spec_fb_part) return OMF_OK;
+  const size_t nt = (size_t)p->nt;
+  Carve c;
+  c.raw(p->d_spec_fb_part, 2 * (size_t)std::max(kFbParts, kWfbParts) * nt);
+  c.zero(p->d_spec_fb_cnt, nt);      // left zero by every launch
+  c.zero(p->d_spec_brgran, 2 * nt);  // epoch 0 is never a launch's tag
+  return make_buffers(p, c, st);
 }
 
 extern "C" {
@@ -2357,6 +1946,7 @@ int omf_plan_create(const int64_t* sizes, const int64_t* offsets, int32_t ntenso
   p->sizes.assign(sizes, sizes + ntensors);
   p->offsets.assign(offsets, offsets + ntensors);
   p->arena_end = offsets[ntensors - 1] + sizes[ntensors - 1];
+  p->spec_last_pw = kSpecPerWave;
   {
     // Co-resident capacity of the encoder (occupancy x CUs over every instantiation); a
     // tensor takes the register-resident path only with half of it as margin.
@@ -2430,13 +2020,8 @@ int omf_plan_destroy(omf_plan* plan) {
   DeviceGuard g(plan->device);
   if (plan->last_ev) (void)hipEventDestroy(plan->last_ev);
   if (plan->d_block) (void)hipFree(plan->d_block);
-  if (plan->d_spec_slots_w) (void)hipFree(plan->d_spec_slots_w);
-  if (plan->d_spec_recs_w) (void)hipFree(plan->d_spec_recs_w);
-  if (plan->d_spec_br_part) (void)hipFree(plan->d_spec_br_part);
-  if (plan->d_spec_br_cnt) (void)hipFree(plan->d_spec_br_cnt);
-  if (plan->d_spec_fb_part) (void)hipFree(plan->d_spec_fb_part);
-  if (plan->d_spec_fb_cnt) (void)hipFree(plan->d_spec_fb_cnt);
-  if (plan->d_spec_brgran) (void)hipFree(plan->d_spec_brgran);
+  for (void* d : plan->d_lazy)
+    if (d) (void)hipFree(d);
   for (auto& e : plan->topk_tables) (void)hipFree(e.dev);
   delete plan;
   return OMF_OK;
@@ -2444,9 +2029,12 @@ int omf_plan_destroy(omf_plan* plan) {
 
 int64_t omf_plan_encode_items(const omf_plan* plan) {
   if (!plan) return -1;
-  if (plan->strategy == 3) return plan->n_spec_blocks;
-  if (plan->strategy == 4) return plan->grid_wgs;
-  return plan->strategy == 2 ? plan->n_ring : plan->n_enc[plan->strategy];
+  switch (plan->strategy) {  // of the strategy's own encoder
+    case kEncBracket: return plan->n_spec_blocks;
+    case kEncGrid: return plan->grid_wgs;
+    case kEncRing: return plan->n_ring;
+    default: return plan->n_enc[plan->strategy];
+  }
 }
 
 int32_t omf_plan_encode_strategy(const omf_plan* plan) { return plan ? plan->strategy : -1; }
@@ -2565,8 +2153,8 @@ int omf_plan_check(omf_plan* plan, void* stream) {
   // ordering against it (and the stream may now be destroyed)
   if (plan->last_valid && plan->last_stream == (hipStream_t)stream) plan->last_valid = false;
   uint32_t err = 0;
-  OMF_HIP(hipMemcpy(&err, plan->d_sync + 4, 4, hipMemcpyDeviceToHost));
-  if (err) OMF_HIP(hipMemset(plan->d_sync + 4, 0, 4));  // report each event once
+  OMF_HIP(hipMemcpy(&err, plan->err_word(), 4, hipMemcpyDeviceToHost));
+  if (err) OMF_HIP(hipMemset(plan->err_word(), 0, 4));  // report each event once
   if (err & 4u)
     return fail(OMF_ETIMEOUT, "QSGD encoder: an on-chip wait exceeded its bound (a ring hand-off, or a "
                               "bracketed-encoder fix waiting for its tensor's norm) and was abandoned; the "
@@ -2582,6 +2170,8 @@ int omf_plan_check(omf_plan* plan, void* stream) {
   return OMF_OK;
 }
 
+}  // extern "C"
+
 static int check_bits(int32_t s) {
   if (s < 0 || s > 30) return fail(OMF_EINVAL, "bit_width must be in [0, 30] (levels = 2^bit_width is an int32 on the wire)");
   return OMF_OK;
@@ -2596,9 +2186,290 @@ struct AccIn {
   float* acc_out;
 };
 
-static int encode_launch(omf_plan* p, const float* x, float alpha, int32_t s, const float* u, uint64_t seed,
-                         uint64_t offset, const float* norm_in, void* q, float* norm_out, bool norm_only, void* stream,
-                         float divisor, float* xout, uint32_t fmt, const AccIn* acc_in);
+// One encode call (the arguments of encode_impl) and its payload width in bytes.
+struct EncCall {
+  const float* x;
+  float alpha;
+  int32_t s;
+  const float* u;
+  uint64_t seed, offset;
+  const float* norm_in;
+  void* q;
+  float* norm_out;
+  bool norm_only;
+  hipStream_t st;
+  float divisor;
+  float* xout;
+  uint32_t fmt;
+  const AccIn* acc_in;
+  int width;
+};
+
+// The choice function's view of a call on plan `p` (omf_plan_layout.h).
+static Call call_of(const omf_plan* p, int32_t s, bool caller_u, bool caller_norms, bool norms_only, uint32_t fmt,
+                    bool divide, bool last_client) {
+  Call c;
+  c.strategy = p->strategy;
+  c.bits = s;
+  c.caller_u = caller_u;
+  c.caller_norms = caller_norms;
+  c.norms_only = norms_only;
+  c.fmt = fmt;
+  c.divide = divide;
+  c.last_client = last_client;
+  c.wide_levels = p->spec_wide != 0;
+  c.fused_bracket = p->spec_fb != 0;
+  c.spec_dbg = p->spec_skip;
+  c.grid_fits = p->grid_wgs > 0 && p->n_spec_blocks <= (int64_t)p->grid_wgs * 4 * kGridNB;
+  return c;
+}
+
+// Launches kernel `k` with exactly its parameter types (the caller checks hipGetLastError).
+template <class... P>
+static void launch(void (*k)(P...), dim3 grid, dim3 blk, size_t lds, hipStream_t st, std::type_identity_t<P>... args) {
+  void* params[] = {&args...};
+  (void)hipLaunchKernel(reinterpret_cast<const void*>(k), grid, blk, params, lds, st);
+}
+
+// What every encoder of this file takes from the call; items, tinfo, epoch and n_items are the launcher's.
+static EncArgs enc_args(const omf_plan* p, const EncCall& c) {
+  EncArgs a{};
+  a.x = c.x; a.u = c.u; a.norm_in = c.norm_in; a.q = c.q; a.norm_out = c.norm_out;
+  a.partials = p->d_partials;
+  a.ticket = reinterpret_cast<uint32_t*>(p->d_sync);
+  a.err = p->err_word();
+  a.counters = reinterpret_cast<uint32_t*>(p->d_sync + p->off_counters);
+  a.gran = reinterpret_cast<uint64_t*>(p->d_sync + p->off_gran);
+  a.alpha = c.alpha;
+  a.fmt = c.fmt;
+  a.levels = (float)(1u << c.s);
+  a.seed_lo = (uint32_t)c.seed; a.seed_hi = (uint32_t)(c.seed >> 32); a.offset = (uint32_t)c.offset;
+  a.wait_ticks = p->wait_ticks;
+  return a;
+}
+
+using EncKernel = void (*)(EncArgs);
+
+// Norms supplied by the caller: one pass over the flat items, 4 blocks of 4 Ki elements per 16 Ki item.
+static void launch_caller_norms(omf_plan* p, const EncCall& c) {
+  static const EncKernel kern[2][2] = {  // [int32 wire][caller uniforms]
+      {qsgd_quant_sub<1, false, 4, false>, qsgd_quant_sub<1, true, 4, false>},
+      {qsgd_quant_sub<4, false, 4, false>, qsgd_quant_sub<4, true, 4, false>}};
+  EncArgs a = enc_args(p, c);
+  a.items = p->d_flat;
+  a.tinfo = p->d_tinfo[0];
+  launch(kern[c.width == 4][c.u != nullptr], dim3((unsigned)(p->n_flat * 4)), dim3(kThreads), 0, c.st, a);
+}
+
+// Grid encoder (strategy 4): one launch of one workgroup per CU.
+static int launch_grid(omf_plan* p, const EncCall& c) {
+  GridArgs ga;
+  ga.e = enc_args(p, c);
+  ga.e.items = p->d_flat;
+  ga.partials = p->d_spec_part;
+  ga.bar = p->d_grid_bar;
+  ga.target = (unsigned long long)(p->grid_launches + 1) * (unsigned long long)p->grid_wgs;
+  ga.nblocks = p->n_spec_blocks;
+  ga.dbg = p->spec_skip;
+  launch(c.width == 1 ? qsgd_encode_grid<1> : qsgd_encode_grid<4>, dim3((unsigned)p->grid_wgs), dim3(1024), 0, c.st, ga,
+         p->d_flat, p->d_begins, p->d_grid_pbeg, p->d_grid_pcnt);
+  OMF_HIP(hipGetLastError());
+  // counted only once the launch is in: the device's monotonic arrival counter advances by
+  // grid_wgs per launch that ran, so a failed launch must not move the host's target
+  ++p->grid_launches;
+  return OMF_OK;
+}
+
+// Bracketed single-read encoder: the bracket (a launch of its own, or the first workgroups of the
+// pass), the pass, the finish.  No host interaction.  Each kernel comes from a table indexed by
+// the variant (wide levels, fused bracket), the payload width, the fused PS step's divide, the
+// value format and the fused last client's payload width.
+static int launch_bracket(omf_plan* p, const EncCall& c, const Choice& ch) {
+  using BracketKernel = void (*)(SpecArgs, const SpecBrItem*);
+  using PassKernel = void (*)(SpecArgs, const SpecBracket*, const int64_t*, const float*);
+  using FusedKernel = void (*)(SpecArgs, const SpecBrItem*, int64_t, const int64_t*);
+  using FinishKernel = void (*)(SpecArgs, const SpecFoldItem*, int32_t, const Item*, const int64_t*, const uint32_t*,
+                                const float4*, const uint32_t*);
+  constexpr int PWW = kSpecPerWaveWide;
+#ifndef OMF_FIX_FT  // experiment builds may override it (scripts/exp/s8_variants.sh)
+#define OMF_FIX_FT 4
+#endif
+  constexpr int FT = OMF_FIX_FT;  // the wide finish: fix threads per wave slot
+  static const BracketKernel k_bracket[2] = {qsgd_spec_bracket<false, false>, qsgd_spec_bracket<false, true>};  // [last client]
+  static const FusedKernel k_fb[2] = {qsgd_spec_quant_fb<1, false>, qsgd_spec_quant_fb<1, true>};  // [divide]
+  static const FusedKernel k_wfb[2][2] = {{qsgd_spec_quant_wfb<1, false>, qsgd_spec_quant_wfb<1, true>},  // [int32 wire][divide]
+                                          {qsgd_spec_quant_wfb<4, false>, qsgd_spec_quant_wfb<4, true>}};
+  static const PassKernel k_pass[2][2] = {{qsgd_spec_quant<1, false>, qsgd_spec_quant<1, true>},  // [int32 wire][divide]
+                                          {qsgd_spec_quant<4, false>, qsgd_spec_quant<4, true>}};
+  static const PassKernel k_pass_half[2] = {qsgd_spec_quant<1, false, kFmtBF16>, qsgd_spec_quant<1, false, kFmtF16>};
+  static const PassKernel k_pass_last[2] = {qsgd_spec_quant<1, true, kFmtF32, 1>,  // [the last client's int32 payload]
+                                            qsgd_spec_quant<1, true, kFmtF32, 4>};
+  static const PassKernel k_pass_wide[2][2][2] = {  // [four waves per workgroup][int32 wire][divide]
+      {{qsgd_spec_quant<1, false, kFmtF32, 0, PWW, 1>, qsgd_spec_quant<1, true, kFmtF32, 0, PWW, 1>},
+       {qsgd_spec_quant<4, false, kFmtF32, 0, PWW, 1>, qsgd_spec_quant<4, true, kFmtF32, 0, PWW, 1>}},
+      {{qsgd_spec_quant<1, false, kFmtF32, 0, PWW>, qsgd_spec_quant<1, true, kFmtF32, 0, PWW>},
+       {qsgd_spec_quant<4, false, kFmtF32, 0, PWW>, qsgd_spec_quant<4, true, kFmtF32, 0, PWW>}}};
+  static const FinishKernel k_finish[2][2] = {{qsgd_spec_finish<1>, qsgd_spec_finish<4>},  // [wide][int32 wire]
+                                              {qsgd_spec_finish<1, PWW, FT>, qsgd_spec_finish<4, PWW, FT>}};
+  // The wide pass's one-wave workgroups reserve 10 KiB of LDS each (unused): 16 per CU, i.e. four
+  // waves per SIMD — 0.556-0.559 ms per Llama-400M s = 8 encode against 0.589 uncapped, 0.565 at 12
+  // KiB, 0.635 at 16 KiB (scripts/exp/occ_ab.sh, two interleaved rounds); OMF_SPEC_LDS_W overrides.
+  // The s <= 4 pass lost under a cap at first (24 KiB: 0.367 against 0.360 ms); since its wave sum left
+  // the LDS and its quad math shed a tenth of its VALU work it reserves 24 KiB (unused): six workgroups
+  // per CU, where the registers would admit eight (profiles/r07_pass_schedule_ab.txt;
+  // OMF_SPEC_LDS overrides).  The fused PS step's pass, which also stores the average, is not capped (not
+  // measured); nor is a pass without the fused bracket.  Wide unfused: one wave per workgroup unless
+  // OMF_SPEC_WPB=4.
+  static const size_t plds_w = [] { const char* v = omf::knob("OMF_SPEC_LDS_W"); return v ? (size_t)atoi(v) : (size_t)10240; }();
+  static const size_t plds_n = [] { const char* v = omf::knob("OMF_SPEC_LDS"); return v ? (size_t)atoi(v) : (size_t)24576; }();
+  static const bool wpb4 = [] { const char* v = omf::knob("OMF_SPEC_WPB"); return v && atoi(v) == 4; }();
+
+  const hipStream_t st = c.st;
+  const AccIn* acc = c.acc_in;
+  const bool wide = ch.wide, div = c.divisor != 0.0f, w4 = c.width == 4;
+  if (wide)
+    if (int r = ensure_wide(p, st)) return r;
+  if (ch.fused)
+    if (int r = ensure_fused_bracket(p, st)) return r;
+  SpecArgs sa;
+  sa.e = enc_args(p, c);
+  sa.e.items = p->d_flat;
+  sa.e.tinfo = p->d_tinfo[1];
+  sa.begins = p->d_begins;
+  sa.sizes = p->d_sizes;
+  sa.br_items = p->d_spec_br_items;
+  sa.fold_items = p->d_spec_fold_items;
+  sa.seg_part = p->d_spec_seg_part;
+  sa.fold_cnt = p->d_spec_cnt;
+  if (++p->spec_epoch >= 0x80000000u) p->spec_epoch = 1;  // 31-bit tags (the norm granule keeps a status bit)
+  sa.epoch = p->spec_epoch;
+  sa.wide = wide ? 1u : 0u;
+  sa.ngran = p->d_spec_ngran;
+  // p->spec_skip: test / experiment switches (omf_plan_set_debug; 0 in production): bit 0
+  // skips the bracket launch (the previous brackets stay), bit 1 the finish launch, bits 2/3
+  // the fix stores / the fix, bit 4 the fold — the payload is then not the encoder's.
+  sa.dbg = p->spec_skip;
+  sa.zsig = wide ? p->spec_zsig_wide : p->spec_zsig;
+  sa.divisor = c.divisor;
+  sa.xout = c.xout;
+  sa.wait_ticks = p->wait_ticks;
+  sa.br = p->d_spec_br;
+  sa.partials = p->d_spec_part;
+  sa.br_part = ch.fused ? p->d_spec_fb_part : p->d_spec_br_part;
+  sa.br_cnt = ch.fused ? p->d_spec_fb_cnt : p->d_spec_br_cnt;
+  sa.brgran = p->d_spec_brgran;
+  p->spec_last_pw = wide ? kSpecPerWaveWide : kSpecPerWave;
+  sa.slots = wide ? p->d_spec_slots_w : p->d_spec_slots;
+  sa.heads = p->d_spec_heads;
+  sa.recs = wide ? p->d_spec_recs_w : p->d_spec_recs;
+  sa.flags = p->d_spec_flags;
+  sa.status = p->d_spec_status;
+  sa.nblocks = p->n_spec_blocks;
+  sa.aq = acc ? acc->q : nullptr;
+  sa.anorm = acc ? acc->norm : nullptr;
+  sa.aout = acc ? acc->acc_out : nullptr;
+  sa.awidth = acc ? acc->width : 0;
+  sa.alevels = acc ? (float)acc->levels : 0.0f;
+  sa.ainv = acc && (acc->levels & (acc->levels - 1)) == 0 ? 1.0f / (float)acc->levels : 0.0f;
+
+  const int64_t nb = p->n_spec_blocks, nt = p->nt;
+  if (ch.bracket_launch)
+    launch(wide ? qsgd_spec_bracket_wide : k_bracket[acc != nullptr], dim3((unsigned)(nt * (wide ? kBrParts : 1))),
+           dim3(kBrThreads), 0, st, sa, sa.br_items);
+  if (ch.fused) {  // the bracket's parts are the pass launch's first workgroups; wide: one-wave workgroups
+    const int64_t nbrw = (wide ? kWfbParts : kFbParts) * nt;
+    if (wide) launch(k_wfb[w4][div], dim3((unsigned)(nbrw + nb * kWaves)), dim3(64), plds_w, st, sa, sa.br_items, nbrw, sa.begins);
+    else launch(k_fb[div], dim3((unsigned)(nbrw + nb)), dim3(kThreads), div ? 0 : plds_n, st, sa, sa.br_items, nbrw, sa.begins);
+  } else if (wide && !wpb4) {
+    launch(k_pass_wide[0][w4][div], dim3((unsigned)(nb * kWaves)), dim3(64), plds_w, st, sa, sa.br, sa.begins, sa.anorm);
+  } else {
+    const PassKernel k = wide                 ? k_pass_wide[1][w4][div]
+                         : c.fmt == kFmtBF16 ? k_pass_half[0]
+                         : c.fmt == kFmtF16  ? k_pass_half[1]
+                         : acc               ? k_pass_last[acc->width == 32]
+                                             : k_pass[w4][div];
+    launch(k, dim3((unsigned)nb), dim3(kThreads), 0, st, sa, sa.br, sa.begins, sa.anorm);
+  }
+  if (!(p->spec_skip & 2u)) {  // (experiment: no finish launch, timings only)
+    // the fold's workgroups first, then the fix: a workgroup's threads share kWaves (x FT, wide) per block
+    const int64_t per = kThreads / (kWaves * (wide ? FT : 1));
+    const int32_t nfold = (int32_t)p->n_spec_fold;
+    launch(k_finish[wide][w4], dim3((unsigned)(nfold + (nb + per - 1) / per)), dim3(kThreads), 0, st, sa, sa.fold_items,
+           nfold, sa.e.items, sa.begins, sa.slots, sa.recs, sa.heads);
+  }
+  OMF_HIP(hipGetLastError());
+  return OMF_OK;
+}
+
+// Single-read ring (omf_qsgd_ring.hip): also the fused PS step's divide + encode in one launch.
+static int launch_ring(omf_plan* p, const EncCall& c) {
+  omf::ring::Args r;
+  r.x = c.x; r.u = c.u; r.q = c.q; r.norm_out = c.norm_out;
+  r.items = p->d_ring; r.tinfo = p->d_ring_t; r.gran = p->d_ring_gran;
+  r.err = p->err_word();
+  r.n_items = p->n_ring;
+  r.alpha = c.alpha;
+  r.fmt = c.fmt;
+  r.round_in = (c.fmt != 0 && c.alpha != 1.0f) ? 1u : 0u;
+  r.divisor = c.divisor;
+  r.divide = c.divisor != 0.0f ? 1u : 0u;
+  r.xout = c.xout;
+  r.levels = (float)(1u << c.s);
+  r.seed_lo = (uint32_t)c.seed; r.seed_hi = (uint32_t)(c.seed >> 32); r.offset = (uint32_t)c.offset;
+  if (++p->ring_epoch == 0) ++p->ring_epoch;
+  r.epoch = p->ring_epoch;
+  r.wait_ticks = p->wait_ticks;
+  r.lds_wait_ticks = p->lds_wait_ticks;
+  r.dbg = p->ring_dbg;
+  r.prof = p->d_ring_prof;
+  const int grid = (int)std::min<int64_t>(p->ring_grid, std::max<int64_t>(p->n_ring, 1));
+  if (omf::ring::launch(p->ring_cfg, c.width, c.u != nullptr, r, grid, c.st) != 0)
+    return fail(OMF_EHIP, "ring encoder launch failed");
+  return OMF_OK;
+}
+
+// Ticket-ordered launch over sequence `strat` (0: register-resident + two-pass, 1: two-pass), and
+// every norms-only pass.  No per-call memset: tickets and arrival counters are reset in-kernel by
+// their last user, and granules carry this launch's epoch.
+static void launch_ordered(omf_plan* p, const EncCall& c, int strat) {
+  static const EncKernel kern[2][5] = {  // [16 rows per thread][norms only, or 1 + 2 x int32 wire + caller uniforms]
+      {qsgd_encode_ordered<1, false, true, 8>, qsgd_encode_ordered<1, false, false, 8>, qsgd_encode_ordered<1, true, false, 8>,
+       qsgd_encode_ordered<4, false, false, 8>, qsgd_encode_ordered<4, true, false, 8>},
+      {qsgd_encode_ordered<1, false, true, 16>, qsgd_encode_ordered<1, false, false, 16>, qsgd_encode_ordered<1, true, false, 16>,
+       qsgd_encode_ordered<4, false, false, 16>, qsgd_encode_ordered<4, true, false, 16>}};
+  EncArgs a = enc_args(p, c);
+  if (++p->epoch == 0) ++p->epoch;
+  a.epoch = p->epoch;
+  a.n_items = (uint32_t)p->n_enc[strat];
+  a.items = p->d_enc[strat];
+  a.tinfo = p->d_tinfo[strat];
+  const int k = c.norm_only ? 0 : 1 + 2 * (c.width == 4) + (c.u != nullptr);
+  launch(kern[p->ev != 8][k], dim3((unsigned)p->n_enc[strat]), dim3(kThreads), 0, c.st, a);
+}
+
+static int encode_launch(omf_plan* p, EncCall c) {
+  if (int r = check_bits(c.s)) return r;
+  c.width = (1 << c.s) <= 127 ? 1 : 4;
+  if (!c.x || !c.norm_out || (!c.norm_only && !c.q)) return fail(OMF_EINVAL, "x, q and norm_out must be non-NULL");
+  if (!aligned(c.x, 16) || (c.u && !aligned(c.u, 16)) || (c.q && !aligned(c.q, c.width == 1 ? 4 : 16)))
+    return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
+  if (!p->d_block) return fail(OMF_EHIP, "the plan's tables are not on the device (an earlier upload failed)");
+  const Choice ch = choose_encoder(call_of(p, c.s, c.u != nullptr, c.norm_in != nullptr, c.norm_only, c.fmt,
+                                           c.divisor != 0.0f, c.acc_in != nullptr));
+  if (!c.norm_only) p->last_encoder = ch.encoder;
+  switch (ch.encoder) {
+    case kEncCallerNorms: launch_caller_norms(p, c); break;
+    case kEncGrid: return launch_grid(p, c);
+    case kEncBracket: return launch_bracket(p, c, ch);
+    case kEncRing:
+      if (int r = launch_ring(p, c)) return r;
+      break;
+    case kEncResident:
+    case kEncOrdered: launch_ordered(p, c, ch.encoder); break;
+  }
+  OMF_HIP(hipGetLastError());
+  return OMF_OK;
+}
 
 static int encode_impl(omf_plan* p, const float* x, float alpha, int32_t s, const float* u, uint64_t seed,
                        uint64_t offset, const float* norm_in, void* q, float* norm_out, bool norm_only, void* stream,
@@ -2607,307 +2478,15 @@ static int encode_impl(omf_plan* p, const float* x, float alpha, int32_t s, cons
   if (fmt < 0 || fmt > 2) return fail(OMF_EINVAL, "value_format must be 0 (fp32), 1 (bf16) or 2 (fp16)");
   DeviceGuard g(p->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  if (int r = plan_enter(p, (hipStream_t)stream)) return r;
-  if (int r = encode_launch(p, x, alpha, s, u, seed, offset, norm_in, q, norm_out, norm_only, stream, divisor, xout,
-                            (uint32_t)fmt, acc_in))
+  const hipStream_t st = (hipStream_t)stream;
+  if (int r = plan_enter(p, st)) return r;
+  if (int r = encode_launch(p, EncCall{x, alpha, s, u, seed, offset, norm_in, q, norm_out, norm_only, st, divisor, xout,
+                                       (uint32_t)fmt, acc_in, 0}))
     return r;
-  return plan_leave(p, (hipStream_t)stream);
+  return plan_leave(p, st);
 }
 
-// Whether a fused PS step with the last client's decode takes the bracketed encoder's one pass
-// (else the caller runs decode-accumulate, then the plain fused step).
-static bool spec_serves(const omf_plan* p, int32_t s, const float* u, float divisor, uint32_t fmt, bool wide_ok);
-
-static int encode_launch(omf_plan* p, const float* x, float alpha, int32_t s, const float* u, uint64_t seed,
-                         uint64_t offset, const float* norm_in, void* q, float* norm_out, bool norm_only, void* stream,
-                         float divisor, float* xout, uint32_t fmt, const AccIn* acc_in) {
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  if (int r = check_bits(s)) return r;
-  const int width = (1 << s) <= 127 ? 1 : 4;
-  if (!x || !norm_out || (!norm_only && !q)) return fail(OMF_EINVAL, "x, q and norm_out must be non-NULL");
-  if (!aligned(x, 16) || (u && !aligned(u, 16)) || (q && !aligned(q, width == 1 ? 4 : 16)))
-    return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
-  DeviceGuard g(p->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;
-  EncArgs a;
-  a.x = x; a.u = u; a.norm_in = norm_in; a.q = q; a.norm_out = norm_out;
-  a.partials = p->d_partials;
-  a.ticket = reinterpret_cast<uint32_t*>(p->d_sync);
-  a.err = reinterpret_cast<uint32_t*>(p->d_sync + 4);
-  a.counters = reinterpret_cast<uint32_t*>(p->d_sync + p->off_counters);
-  a.gran = reinterpret_cast<uint64_t*>(p->d_sync + p->off_gran);
-  a.alpha = alpha;
-  a.fmt = fmt;
-  a.levels = (float)(1u << s);
-  a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.offset = (uint32_t)offset;
-  a.wait_ticks = p->wait_ticks;
-  const dim3 blk(kThreads);
-  if (norm_in && !norm_only) {
-    a.items = p->d_flat;
-    a.tinfo = p->d_tinfo[0];
-    const dim3 grid4((unsigned)(p->n_flat * 4));  // 4 blocks of 4 Ki elements per 16 Ki item
-    p->last_encoder = 5;
-    if (width == 1) {
-      if (u) hipLaunchKernelGGL((qsgd_quant_sub<1, true, 4, false>), grid4, blk, 0, st, a);
-      else hipLaunchKernelGGL((qsgd_quant_sub<1, false, 4, false>), grid4, blk, 0, st, a);
-    } else {
-      if (u) hipLaunchKernelGGL((qsgd_quant_sub<4, true, 4, false>), grid4, blk, 0, st, a);
-      else hipLaunchKernelGGL((qsgd_quant_sub<4, false, 4, false>), grid4, blk, 0, st, a);
-    }
-    OMF_HIP(hipGetLastError());
-    return OMF_OK;
-  }
-  // Grid encoder (strategy 4): on-device draws, any value format and width, arenas of at most
-  // grid_wgs x 4 x kGridNB blocks of 4 Ki (larger ones, caller uniforms and the fused PS step
-  // take the ring).  One launch.
-  if (p->strategy == 4 && !norm_only && !u && divisor == 0.0f && p->grid_wgs > 0 &&
-      p->n_spec_blocks <= (int64_t)p->grid_wgs * 4 * kGridNB) {
-    GridArgs ga;
-    a.items = p->d_flat;
-    ga.e = a;
-    ga.partials = p->d_spec_part;
-    ga.bar = p->d_grid_bar;
-    ga.target = (unsigned long long)(p->grid_launches + 1) * (unsigned long long)p->grid_wgs;
-    ga.nblocks = p->n_spec_blocks;
-    ga.dbg = p->spec_skip;
-    const dim3 gg((unsigned)p->grid_wgs), gblk(1024);
-    if (width == 1)
-      hipLaunchKernelGGL(qsgd_encode_grid<1>, gg, gblk, 0, st, ga, (const Item*)p->d_flat, (const int64_t*)p->d_begins,
-                         (const uint32_t*)p->d_grid_pbeg, (const uint32_t*)p->d_grid_pcnt);
-    else
-      hipLaunchKernelGGL(qsgd_encode_grid<4>, gg, gblk, 0, st, ga, (const Item*)p->d_flat, (const int64_t*)p->d_begins,
-                         (const uint32_t*)p->d_grid_pbeg, (const uint32_t*)p->d_grid_pcnt);
-    OMF_HIP(hipGetLastError());
-    // counted only once the launch is in: the device's monotonic arrival counter advances by
-    // grid_wgs per launch that ran, so a failed launch must not move the host's target
-    ++p->grid_launches;
-    p->last_encoder = 4;
-    return OMF_OK;
-  }
-  // Bracketed single-read encoder: fp32 / bf16 / fp16 values with on-device draws at s <= 4, and
-  // fp32 at s = 5-8 with wide levels (the default; int8 at 5-6, the int32 wire at 7-8); the rest
-  // (wide levels off: the int32 wire on the ring, s = 5-6 and caller uniforms on the two-pass
-  // encoder; the fused PS step is fp32).  No host interaction.
-  if (!norm_only && spec_serves(p, s, u, divisor, fmt, acc_in == nullptr)) {
-    // (the fused PS step too: the pass divides, stores the average and quantises it)
-    SpecArgs sa;
-    a.items = p->d_flat;
-    a.tinfo = p->d_tinfo[1];
-    sa.e = a;
-    p->last_encoder = 3;
-    sa.begins = p->d_begins;
-    sa.sizes = p->d_sizes;
-    sa.br_items = p->d_spec_br_items;
-    sa.fold_items = p->d_spec_fold_items;
-    sa.seg_part = p->d_spec_seg_part;
-    sa.fold_cnt = p->d_spec_cnt;
-    if (++p->spec_epoch >= 0x80000000u) p->spec_epoch = 1;  // 31-bit tags (the norm granule keeps a status bit)
-    sa.epoch = p->spec_epoch;
-    sa.wide = s > kSpecMaxBits ? 1u : 0u;
-    sa.ngran = p->d_spec_ngran;
-    sa.dbg = p->spec_skip;
-    sa.zsig = s > kSpecMaxBits ? p->spec_zsig_wide : p->spec_zsig;
-    sa.divisor = divisor;
-    sa.xout = xout;
-    sa.wait_ticks = p->wait_ticks;
-    sa.br = p->d_spec_br;
-    sa.partials = p->d_spec_part;
-    const bool wide = s > kSpecMaxBits;
-    if (wide && !p->d_spec_slots_w) {  // once per plan: the wide-level list capacity
-      OMF_HIP(hipMalloc(&p->d_spec_slots_w, 4 * (size_t)spec_slot_words(kSpecPerWaveWide) * (size_t)p->n_spec_blocks));
-      OMF_HIP(hipMalloc(&p->d_spec_recs_w, 32 * (size_t)kWaves * kSpecPerWaveWide * (size_t)p->n_spec_blocks));
-      OMF_HIP(hipMalloc(&p->d_spec_br_part, 16 * (size_t)kBrParts * (size_t)p->nt));
-      OMF_HIP(hipMalloc(&p->d_spec_br_cnt, 4 * (size_t)p->nt));
-      OMF_HIP(hipMemsetAsync(p->d_spec_br_cnt, 0, 4 * (size_t)p->nt, st));  // left zero by every launch
-    }
-    const bool fb = p->spec_fb && !wide && !acc_in && fmt == 0 && width == 1 && !(p->spec_skip & 1u);
-    const bool wfb = p->spec_fb && wide && !acc_in && fmt == 0 && !(p->spec_skip & 1u);  // wide levels
-    if ((fb || wfb) && !p->d_spec_fb_part) {  // once per plan: the fused bracket's sums, counters and granules
-      OMF_HIP(hipMalloc(&p->d_spec_fb_part, 16 * (size_t)std::max(kFbParts, kWfbParts) * (size_t)p->nt));
-      OMF_HIP(hipMalloc(&p->d_spec_fb_cnt, 4 * (size_t)p->nt));
-      OMF_HIP(hipMalloc(&p->d_spec_brgran, 16 * (size_t)p->nt));
-      OMF_HIP(hipMemsetAsync(p->d_spec_fb_cnt, 0, 4 * (size_t)p->nt, st));  // left zero by every launch
-      OMF_HIP(hipMemsetAsync(p->d_spec_brgran, 0, 16 * (size_t)p->nt, st));  // epoch 0 is never a launch's
-    }
-    sa.br_part = fb || wfb ? p->d_spec_fb_part : p->d_spec_br_part;
-    sa.br_cnt = fb || wfb ? p->d_spec_fb_cnt : p->d_spec_br_cnt;
-    sa.brgran = p->d_spec_brgran;
-    p->spec_last_pw = wide ? kSpecPerWaveWide : kSpecPerWave;
-    sa.slots = wide ? p->d_spec_slots_w : p->d_spec_slots;
-    sa.heads = p->d_spec_heads;
-    sa.recs = wide ? p->d_spec_recs_w : p->d_spec_recs;
-    sa.flags = p->d_spec_flags;
-    sa.status = p->d_spec_status;
-    sa.nblocks = p->n_spec_blocks;
-    sa.aq = acc_in ? acc_in->q : nullptr;
-    sa.anorm = acc_in ? acc_in->norm : nullptr;
-    sa.aout = acc_in ? acc_in->acc_out : nullptr;
-    sa.awidth = acc_in ? acc_in->width : 0;
-    sa.alevels = acc_in ? (float)acc_in->levels : 0.0f;
-    sa.ainv = acc_in && (acc_in->levels & (acc_in->levels - 1)) == 0 ? 1.0f / (float)acc_in->levels : 0.0f;
-    const dim3 gbr((unsigned)(p->n_spec_br * (s > kSpecMaxBits ? kBrParts : 1))), gb((unsigned)p->n_spec_blocks);
-    // p->spec_skip: test / experiment switches (omf_plan_set_debug; 0 in production): bit 0
-    // skips the bracket launch (the previous brackets stay), bit 1 the finish launch, bits 2/3
-    // the fix stores / the fix, bit 4 the fold — the payload is then not the encoder's.
-    const bool div = divisor != 0.0f;
-    // The wide pass's one-wave workgroups reserve 10 KiB of LDS each (unused): 16 per CU, i.e. four
-    // waves per SIMD — 0.556-0.559 ms per Llama-400M s = 8 encode against 0.589 uncapped, 0.565 at 12
-    // KiB, 0.635 at 16 KiB (scripts/exp/occ_ab.sh, two interleaved rounds); OMF_SPEC_LDS_W overrides.
-    // The s <= 4 pass lost under a cap at first (24 KiB: 0.367 against 0.360 ms); it reserves 24 KiB since
-    // its wave sum left the LDS and its quad math shed a tenth of its VALU work (below).
-    static const size_t plds_w = [] { const char* v = omf::knob("OMF_SPEC_LDS_W"); return v ? (size_t)atoi(v) : (size_t)10240; }();
-    if (fb) {  // the bracket folded into the pass (its first workgroups)
-      const int64_t nbrw = (int64_t)kFbParts * p->n_spec_br;
-      const dim3 gfb((unsigned)(nbrw + p->n_spec_blocks));
-      // The plain pass reserves 24 KiB of LDS per workgroup (unused): six workgroups per CU, where the
-      // registers would admit eight (profiles/r07_pass_schedule_ab.txt; OMF_SPEC_LDS
-      // overrides).  The fused PS step's pass, which also stores the average, is not capped (not measured).
-      static const size_t plds_n = [] { const char* v = omf::knob("OMF_SPEC_LDS"); return v ? (size_t)atoi(v) : (size_t)24576; }();
-      if (div) hipLaunchKernelGGL((qsgd_spec_quant_fb<1, true>), gfb, blk, 0, st, sa, sa.br_items, nbrw, sa.begins);
-      else hipLaunchKernelGGL((qsgd_spec_quant_fb<1, false>), gfb, blk, plds_n, st, sa, sa.br_items, nbrw, sa.begins);
-    } else if (wfb) {  // wide levels: the bracket's one-wave parts first, then the pass's one-wave blocks
-      const int64_t nbrw = (int64_t)kWfbParts * p->n_spec_br;
-      const dim3 gw((unsigned)(nbrw + p->n_spec_blocks * kWaves)), bw(64);
-      if (width == 1 && !div) hipLaunchKernelGGL((qsgd_spec_quant_wfb<1, false>), gw, bw, plds_w, st, sa, sa.br_items, nbrw, sa.begins);
-      else if (width == 1) hipLaunchKernelGGL((qsgd_spec_quant_wfb<1, true>), gw, bw, plds_w, st, sa, sa.br_items, nbrw, sa.begins);
-      else if (!div) hipLaunchKernelGGL((qsgd_spec_quant_wfb<4, false>), gw, bw, plds_w, st, sa, sa.br_items, nbrw, sa.begins);
-      else hipLaunchKernelGGL((qsgd_spec_quant_wfb<4, true>), gw, bw, plds_w, st, sa, sa.br_items, nbrw, sa.begins);
-    } else if (!(p->spec_skip & 1u)) {
-      if (wide) hipLaunchKernelGGL(qsgd_spec_bracket_wide, gbr, dim3(kBrThreads), 0, st, sa, sa.br_items);
-      else if (sa.aq) hipLaunchKernelGGL((qsgd_spec_bracket<false, true>), gbr, dim3(kBrThreads), 0, st, sa, sa.br_items);
-      else hipLaunchKernelGGL((qsgd_spec_bracket<false, false>), gbr, dim3(kBrThreads), 0, st, sa, sa.br_items);
-    }
-    const float* an = sa.anorm;
-    const int aw = acc_in ? (acc_in->width == 32 ? 4 : 1) : 0;
-    constexpr int PWW = kSpecPerWaveWide;
-    if (fb || wfb) {
-      // (the pass ran above)
-    } else if (wide) {  // fp32, no fused last client (spec_serves); one wave per workgroup unless OMF_SPEC_WPB=4
-      static const bool wpb4 = [] { const char* v = omf::knob("OMF_SPEC_WPB"); return v && atoi(v) == 4; }();
-      const dim3 g1((unsigned)(p->n_spec_blocks * kWaves)), b1(64);
-      if (wpb4) {
-        if (width == 1 && !div) hipLaunchKernelGGL((qsgd_spec_quant<1, false, kFmtF32, 0, PWW>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-        else if (width == 1) hipLaunchKernelGGL((qsgd_spec_quant<1, true, kFmtF32, 0, PWW>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-        else if (!div) hipLaunchKernelGGL((qsgd_spec_quant<4, false, kFmtF32, 0, PWW>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-        else hipLaunchKernelGGL((qsgd_spec_quant<4, true, kFmtF32, 0, PWW>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-      } else {
-        if (width == 1 && !div) hipLaunchKernelGGL((qsgd_spec_quant<1, false, kFmtF32, 0, PWW, 1>), g1, b1, plds_w, st, sa, sa.br, sa.begins, an);
-        else if (width == 1) hipLaunchKernelGGL((qsgd_spec_quant<1, true, kFmtF32, 0, PWW, 1>), g1, b1, plds_w, st, sa, sa.br, sa.begins, an);
-        else if (!div) hipLaunchKernelGGL((qsgd_spec_quant<4, false, kFmtF32, 0, PWW, 1>), g1, b1, plds_w, st, sa, sa.br, sa.begins, an);
-        else hipLaunchKernelGGL((qsgd_spec_quant<4, true, kFmtF32, 0, PWW, 1>), g1, b1, plds_w, st, sa, sa.br, sa.begins, an);
-      }
-    } else if (fmt == kFmtBF16) hipLaunchKernelGGL((qsgd_spec_quant<1, false, kFmtBF16>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (fmt == kFmtF16) hipLaunchKernelGGL((qsgd_spec_quant<1, false, kFmtF16>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (width == 1 && !div) hipLaunchKernelGGL((qsgd_spec_quant<1, false>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (width == 1 && aw == 1) hipLaunchKernelGGL((qsgd_spec_quant<1, true, kFmtF32, 1>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (width == 1 && aw == 4) hipLaunchKernelGGL((qsgd_spec_quant<1, true, kFmtF32, 4>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (width == 1) hipLaunchKernelGGL((qsgd_spec_quant<1, true>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else if (!div) hipLaunchKernelGGL((qsgd_spec_quant<4, false>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    else hipLaunchKernelGGL((qsgd_spec_quant<4, true>), gb, blk, 0, st, sa, sa.br, sa.begins, an);
-    if (p->spec_skip & 2u) {  // experiment: no finish launch (timings only)
-      OMF_HIP(hipGetLastError());
-      return OMF_OK;
-    }
-    const int32_t nfold = (int32_t)p->n_spec_fold;
-    if (wide) {
-#ifndef OMF_FIX_FT  // experiment builds may override it (scripts/exp/s8_variants.sh)
-#define OMF_FIX_FT 4
-#endif
-      constexpr int FT = OMF_FIX_FT, BPW = kThreads / (kWaves * FT);  // fix: 16 blocks per workgroup
-      const dim3 gw((unsigned)(nfold + (p->n_spec_blocks + BPW - 1) / BPW));
-      if (width == 1)
-        hipLaunchKernelGGL((qsgd_spec_finish<1, PWW, FT>), gw, blk, 0, st, sa, (const SpecFoldItem*)sa.fold_items, nfold,
-                           (const Item*)a.items, (const int64_t*)sa.begins, (const uint32_t*)sa.slots,
-                           (const float4*)sa.recs, (const uint32_t*)sa.heads);
-      else
-        hipLaunchKernelGGL((qsgd_spec_finish<4, PWW, FT>), gw, blk, 0, st, sa, (const SpecFoldItem*)sa.fold_items, nfold,
-                           (const Item*)a.items, (const int64_t*)sa.begins, (const uint32_t*)sa.slots,
-                           (const float4*)sa.recs, (const uint32_t*)sa.heads);
-      OMF_HIP(hipGetLastError());
-      return OMF_OK;
-    }
-    const dim3 gfin((unsigned)(nfold + (p->n_spec_blocks + kThreads / kWaves - 1) / (kThreads / kWaves)));  // fix: 64 blocks per workgroup
-    if (width == 1)
-      hipLaunchKernelGGL(qsgd_spec_finish<1>, gfin, blk, 0, st, sa, (const SpecFoldItem*)sa.fold_items, nfold,
-                         (const Item*)a.items, (const int64_t*)sa.begins, (const uint32_t*)sa.slots,
-                         (const float4*)sa.recs, (const uint32_t*)sa.heads);
-    else
-      hipLaunchKernelGGL(qsgd_spec_finish<4>, gfin, blk, 0, st, sa, (const SpecFoldItem*)sa.fold_items, nfold,
-                         (const Item*)a.items, (const int64_t*)sa.begins, (const uint32_t*)sa.slots,
-                         (const float4*)sa.recs, (const uint32_t*)sa.heads);
-    OMF_HIP(hipGetLastError());
-    return OMF_OK;
-  }
-  // The ring also serves the fused PS step (divide + encode in one launch) under any strategy,
-  // and — with wide levels off (omf_plan_set_wide_levels) — the bracketed plans' int32-wire
-  // encodes (s >= 7, fp32, on-device draws): Llama-400M s = 8 0.68 ms against 0.74 for the
-  // two-pass encoder, whose second pass rewrites the 4 N payload after re-reading x (round 4).
-  // With wide levels on (the default) those take the bracketed encoder above.  bf16 / fp16
-  // values and caller uniforms stay on the two-pass encoder (0.61 / 0.78 ms against the ring's
-  // 0.70 / 0.83).
-  const bool wide_ring = p->strategy == 3 && width == 4 && !u && fmt == 0;
-  if ((p->strategy == 2 || p->strategy == 4 || divisor != 0.0f || wide_ring) && !norm_only) {
-    omf::ring::Args r;
-    r.x = x; r.u = u; r.q = q; r.norm_out = norm_out;
-    r.items = p->d_ring; r.tinfo = p->d_ring_t; r.gran = p->d_ring_gran;
-    r.err = reinterpret_cast<uint32_t*>(p->d_sync + 4);
-    r.n_items = p->n_ring;
-    r.alpha = alpha;
-    r.fmt = fmt;
-    r.round_in = (fmt != 0 && alpha != 1.0f) ? 1u : 0u;
-    r.divisor = divisor;
-    r.divide = divisor != 0.0f ? 1u : 0u;
-    r.xout = xout;
-    r.levels = (float)(1u << s);
-    r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32); r.offset = (uint32_t)offset;
-    if (++p->ring_epoch == 0) ++p->ring_epoch;
-    r.epoch = p->ring_epoch;
-    r.wait_ticks = p->wait_ticks;
-    r.lds_wait_ticks = p->lds_wait_ticks;
-    r.dbg = p->ring_dbg;
-    r.prof = p->d_ring_prof;
-    const int grid = (int)std::min<int64_t>(p->ring_grid, std::max<int64_t>(p->n_ring, 1));
-    p->last_encoder = 2;
-    if (omf::ring::launch(p->ring_cfg, width, u != nullptr, r, grid, st) != 0)
-      return fail(OMF_EHIP, "ring encoder launch failed");
-    OMF_HIP(hipGetLastError());
-    return OMF_OK;
-  }
-  // No per-call memset: tickets and arrival counters are reset in-kernel by their last
-  // user, and granules carry this launch's epoch.
-  const int strat = p->strategy >= 2 ? 1 : p->strategy;  // norms-only passes use the two-pass tables
-  if (++p->epoch == 0) ++p->epoch;
-  a.epoch = p->epoch;
-  a.n_items = (uint32_t)p->n_enc[strat];
-  a.items = p->d_enc[strat];
-  a.tinfo = p->d_tinfo[strat];
-  const dim3 grid((unsigned)p->n_enc[strat]);
-  if (!norm_only) p->last_encoder = strat;
-#define OMF_ENC(EV)                                                                              \
-  do {                                                                                           \
-    if (norm_only) {                                                                             \
-      hipLaunchKernelGGL((qsgd_encode_ordered<1, false, true, EV>), grid, blk, 0, st, a);        \
-    } else if (width == 1) {                                                                     \
-      if (u) hipLaunchKernelGGL((qsgd_encode_ordered<1, true, false, EV>), grid, blk, 0, st, a); \
-      else hipLaunchKernelGGL((qsgd_encode_ordered<1, false, false, EV>), grid, blk, 0, st, a);  \
-    } else {                                                                                     \
-      if (u) hipLaunchKernelGGL((qsgd_encode_ordered<4, true, false, EV>), grid, blk, 0, st, a); \
-      else hipLaunchKernelGGL((qsgd_encode_ordered<4, false, false, EV>), grid, blk, 0, st, a);  \
-    }                                                                                            \
-  } while (0)
-  if (p->ev == 8) OMF_ENC(8);
-  else OMF_ENC(16);
-#undef OMF_ENC
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
-static bool spec_serves(const omf_plan* p, int32_t s, const float* u, float divisor, uint32_t fmt, bool wide_ok) {
-  if (p->strategy != 3 || u || s < kSpecMinBits) return false;
-  if (s <= kSpecMaxBits) return fmt == 0 || divisor == 0.0f;
-  return wide_ok && p->spec_wide && s <= kSpecMaxBitsWide && fmt == 0;  // fp32 wide levels
-}
+extern "C" {
 
 int omf_qsgd_encode(omf_plan* plan, const float* x, float alpha, int32_t bit_width, const float* u, uint64_t seed,
                     uint64_t offset, const float* norm_in, void* q_out, float* norm_out, void* stream) {
@@ -2978,7 +2557,8 @@ int omf_ps_accumulate_apply_encode(omf_plan* p, const float* acc, const void* q_
   DeviceGuard g(p->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
-  if (spec_serves(p, bit_width, u, divisor, 0u, false)) {  // one pass: acc and the last payload read once
+  // one pass (acc and the last payload read once) where the bracketed encoder serves the call
+  if (choose_encoder(call_of(p, bit_width, u != nullptr, false, false, 0u, true, true)).encoder == kEncBracket) {
     const AccIn ai{q_in, width_in, levels_in, norm_in, acc_out};
     return encode_impl(p, acc, 1.0f, bit_width, u, seed, offset, nullptr, q_out, norm_out, false, stream, divisor,
                        avg_out, 0, &ai);

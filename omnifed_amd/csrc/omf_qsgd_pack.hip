@@ -17,12 +17,13 @@
 
 #include "../../include/omf_codec.h"
 #include "omf_common.h"
+#include "omf_plan.h"
 
 using namespace omf;
 
 namespace {
 
-constexpr int64_t kTableBlk = 4096;  // elements per decoder-table block (omf_qsgd.hip kDecBlk)
+constexpr int64_t kTableBlk = omf::plan_layout::kDecBlk;  // elements per decoder-table block
 constexpr int kGroupBlk = 32 * kThreads;  // elements per workgroup of the pack and the decode
 static_assert(kGroupBlk == 2 * kTableBlk, "two table blocks per workgroup");
 
@@ -249,30 +250,19 @@ void dispatch_decode(int b, dim3 g, hipStream_t st, const uint32_t* packed, cons
 
 }  // namespace
 
-namespace omf_plan_access {
-int device(const omf_plan* p);
-int32_t ntensors(const omf_plan* p);
-int64_t arena_end(const omf_plan* p);
-const int64_t* d_sizes(const omf_plan* p);
-const int64_t* d_begins(const omf_plan* p);
-const std::vector<int64_t>& offsets(const omf_plan* p);
-const uint32_t* dec_blocks(const omf_plan* p, int64_t* n, int64_t* block_elems);
-}  // namespace omf_plan_access
-
 namespace {
 
 // The plan's arena for the packed wire, or an error: every tensor offset a multiple of 32
 // elements (a tensor's stream then starts on a word, and a 32-element group lies in one tensor).
 int packed_arena(const omf_plan* plan, ArenaArgs* a, dim3* grid) {
-  for (const int64_t o : omf_plan_access::offsets(plan))
+  for (const int64_t o : plan->offsets)
     if (o & 31) return fail(OMF_EINVAL, "the packed wire needs tensor offsets that are multiples of 32 elements");
-  int64_t tblk = 0;
-  a->binfo = omf_plan_access::dec_blocks(plan, &a->nbinfo, &tblk);
-  if (tblk != kTableBlk) return fail(OMF_EINVAL, "packed wire: decoder table block size mismatch (library build)");
-  a->begins = omf_plan_access::d_begins(plan);
-  a->sizes = omf_plan_access::d_sizes(plan);
-  a->nt = omf_plan_access::ntensors(plan);
-  a->arena_end = omf_plan_access::arena_end(plan);
+  a->binfo = plan->d_dec_binfo;
+  a->nbinfo = plan->n_dec_blocks;
+  a->begins = plan->d_begins;
+  a->sizes = plan->d_sizes;
+  a->nt = plan->nt;
+  a->arena_end = plan->arena_end;
   *grid = dim3((unsigned)((a->arena_end + kGroupBlk - 1) / kGroupBlk));
   return OMF_OK;
 }
@@ -301,7 +291,7 @@ int omf_qsgd_pack(omf_plan* plan, const void* q, int32_t width, int32_t levels, 
   ArenaArgs a;
   dim3 grid;
   if (const int rc = packed_arena(plan, &a, &grid)) return rc;
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
   if (width == 8) dispatch_pack<1>(b, grid, st, q, a, levels, packed);
@@ -320,7 +310,7 @@ int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t level
   ArenaArgs a;
   dim3 grid;
   if (const int rc = packed_arena(plan, &a, &grid)) return rc;
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
   const bool pow2 = (levels & (levels - 1)) == 0;

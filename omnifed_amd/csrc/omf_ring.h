@@ -1,34 +1,17 @@
 // omf_ring.h — internal interface of the single-read QSGD encoder (omf_qsgd_ring.hip).
 //
-// Not part of the C ABI: the plan (omf_qsgd.hip) builds the work-item tables and calls
-// omf::ring::launch.  DESIGN.md §3.1 describes the algorithm.
+// Not part of the C ABI: the plan (omf_qsgd.hip) uploads the work-item tables that
+// omf_plan_layout.cpp builds and calls omf::ring::launch.  DESIGN.md §3.1 describes the algorithm.
 #pragma once
 
 #include "omf_common.h"
+#include "omf_plan_layout.h"
 
 namespace omf {
 namespace ring {
 
-// Work-item flags: a chunk publishes its partial sum of squares and/or quantises.
-//   kPublish | kQuant  HOLD   read once: partial, keep the chunk on chip, quantise later
-//   kPublish           NORM   partial only (first pass of a tensor too large to hold)
-//   kQuant             QUANT  second pass of such a tensor: re-read and quantise
-enum : int32_t { kPublish = 1, kQuant = 2 };
-
-// 64 bytes = one scalar load: the tensor's fields ride along so the hot loops never make
-// a second, dependent table read.
-struct Item {
-  int64_t begin, end;    // arena element range (one chunk of one tensor)
-  int64_t tbegin, tn;    // the tensor's range
-  int32_t tensor, flags, chunk, nchunks;
-  int32_t gbase, pad[3];  // the tensor's first granule
-};
-
-struct Tensor {
-  int64_t begin, n;
-  int32_t nchunks, gbase;  // partial granules of this tensor: gran[gbase .. gbase + nchunks)
-  int32_t pad[2];
-};
+// The work-item records (Item, Tensor) and flags (kPublish, kQuant) are in omf_plan_layout.h, with
+// the builders of their tables.
 
 struct Args {
   const float* x;

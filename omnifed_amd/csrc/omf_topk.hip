@@ -53,6 +53,7 @@
 #include "../../include/omf_codec.h"
 #include "../../include/omf_codec_experimental.h"
 #include "omf_common.h"
+#include "omf_plan.h"
 
 using namespace omf;
 
@@ -121,11 +122,7 @@ struct BucketRec {
   uint32_t count_tensor;
 };
 
-// Mirrors the QSGD plan's item / tensor tables (omf_qsgd.hip); only the fields used here.
-struct Item {
-  int64_t begin, end;
-  int32_t tensor, kind, chunk, pad;
-};
+using Item = omf::plan_layout::Item;  // the plan's flat items (omf_plan_layout.h)
 
 __device__ __forceinline__ uint32_t mag_key(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
@@ -2526,23 +2523,7 @@ __global__ __launch_bounds__(kThreads) void topk_dec_overflow(uint32_t* __restri
 }  // namespace
 
 // ---------------------------------------------------------------- host side
-// Plan internals (defined in omf_qsgd.hip): accessed through these helpers.
-namespace omf_plan_access {
-const void* flat_items(const omf_plan* p, int64_t* n);
-int32_t ntensors(const omf_plan* p);
-int device(const omf_plan* p);
-int64_t arena_end(const omf_plan* p);
-const int64_t* d_sizes(const omf_plan* p);
-const int64_t* d_begins(const omf_plan* p);
-const std::vector<int64_t>& sizes(const omf_plan* p);
-const std::vector<int64_t>& offsets(const omf_plan* p);
-void* topk_table(omf_plan* p, uint64_t key, size_t bytes, bool* fresh, uint64_t** host);
-void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes, bool* fresh, uint64_t** host);
-omf::TopkKnobs& topk_knobs(omf_plan* p);
-uint32_t* err_word(omf_plan* p);
-int order_enter(omf_plan* p, hipStream_t st);
-int order_leave(omf_plan* p, hipStream_t st);
-}  // namespace omf_plan_access
+// (the plan: omf_plan.h)
 
 namespace {
 
@@ -2605,8 +2586,8 @@ int topk_group_count(const omf_plan* p, const TopkKnobs& kn) {
   // 1.089 ms with one group, 1.156 / 1.192 / 1.266 ms with 2 / 3 / 4 (the latency-bound kernels
   // do not shrink with their group, and their random stores slow the streaming pass beside them).
   int g = kn.groups;
-  if (omf_plan_access::arena_end(p) < ((int64_t)1 << 24)) g = 1;  // small arenas: launch-bound
-  return std::max(1, std::min(g, std::min(16, omf_plan_access::ntensors(p))));
+  if (p->arena_end < ((int64_t)1 << 24)) g = 1;  // small arenas: launch-bound
+  return std::max(1, std::min(g, std::min(16, p->nt)));
 }
 
 std::vector<Group> make_groups(const std::vector<int64_t>& sizes, double ratio, int64_t max_runs, int G) {
@@ -2655,7 +2636,7 @@ std::vector<Group> make_groups(const std::vector<int64_t>& sizes, double ratio, 
 // OMF_TOPK_SCATTER_SMALL, OMF_TOPK_PLANNED_SCATTER),
 // unless omf_plan_set_topk set them first.
 const TopkKnobs& knobs(omf_plan* p) {
-  TopkKnobs& k = omf_plan_access::topk_knobs(p);
+  TopkKnobs& k = p->topk_knobs;
   if (k.init) return k;
   k.init = true;
   if (const char* e = omf::knob("OMF_TOPK_GROUPS")) k.groups = std::max(1, std::atoi(e));
@@ -2687,20 +2668,20 @@ const TopkKnobs& knobs(omf_plan* p) {
 }
 
 bool global_path(const omf_plan* p) {
-  if (omf_plan_access::ntensors(p) > 256) return false;
-  for (int64_t n : omf_plan_access::sizes(p))
+  if (p->nt > 256) return false;
+  for (int64_t n : p->sizes)
     if (n > (int64_t)1 << 25) return false;
   return true;
 }
 
 size_t sort_tmp_bytes(const omf_plan* p) {
-  const int64_t size = omf_plan_access::arena_end(p);
-  const int32_t nt = omf_plan_access::ntensors(p);
+  const int64_t size = p->arena_end;
+  const int32_t nt = p->nt;
   size_t bytes = 0;
   uint64_t* dummy = nullptr;
   if (global_path(p)) {
     (void)dummy;
-    bytes = 4 * (size_t)kRadixDigits * tail_grid(omf_plan_access::device(p));  // the exact tail's digit table
+    bytes = 4 * (size_t)kRadixDigits * tail_grid(p->device);  // the exact tail's digit table
   } else {
     uint32_t* off = nullptr;
     (void)rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, dummy, dummy, (unsigned int)size, (unsigned int)nt,
@@ -2720,7 +2701,7 @@ struct WsLayout {
 // Bucket-table slots for any ratio (k <= n).
 size_t bucket_slots_max(const omf_plan* p) {
   size_t nb = 0;
-  for (int64_t n : omf_plan_access::sizes(p)) nb += (size_t)bucket_slots(n);
+  for (int64_t n : p->sizes) nb += (size_t)bucket_slots(n);
   return nb;
 }
 
@@ -2736,7 +2717,7 @@ WsLayout layout(const omf_plan* p) {
   };
   thread_local Key key{nullptr, -1, -1};
   thread_local WsLayout cached;
-  const Key k{p, omf_plan_access::arena_end(p), omf_plan_access::ntensors(p)};
+  const Key k{p, p->arena_end, p->nt};
   if (k.p != key.p || k.ae != key.ae || k.nt != key.nt) {
     cached = layout_uncached(p);
     key = k;
@@ -2745,8 +2726,8 @@ WsLayout layout(const omf_plan* p) {
 }
 
 WsLayout layout_uncached(const omf_plan* p) {
-  const int32_t nt = omf_plan_access::ntensors(p);
-  const int64_t ae = omf_plan_access::arena_end(p);
+  const int32_t nt = p->nt;
+  const int64_t ae = p->arena_end;
   WsLayout L;
   size_t o = 0;
   L.hist = o; o = align256(o + 4 * (size_t)nt * kBins);
@@ -2764,8 +2745,7 @@ WsLayout layout_uncached(const omf_plan* p) {
   L.seg_b = o; o = align256(o + 4 * (size_t)nt);
   L.seg_e = o; o = align256(o + 4 * (size_t)nt);
   L.cstart = o; o = align256(o + 8 * (size_t)nt);
-  int64_t n_items = 0;
-  (void)omf_plan_access::flat_items(p, &n_items);
+  const int64_t n_items = p->n_flat;
   L.sub_cnt = o; o = align256(o + 4 * (size_t)n_items * kSubsPerItem);
   L.item_cnt = o; o = align256(o + 4 * (size_t)n_items);
   L.item_off = o; o = align256(o + 4 * (size_t)n_items);
@@ -2793,7 +2773,7 @@ WsLayout layout_uncached(const omf_plan* p) {
 }
 
 // Per (plan, ratio, sample size) constant tables of the encoder, plan-owned
-// (omf_plan_access::topk_table), made once: topk_setup's per-tensor k / offsets / item ranges /
+// (topk_table, omf_plan.h), made once: topk_setup's per-tensor k / offsets / item ranges /
 // bucket and super-item bases, the sampling blocks' (tensor, first run) map, the sample
 // histograms gh (zeroed here once, left zeroed by every call) and the arrival counters of the
 // sample (per tensor) and plan kernels (likewise).
@@ -2824,14 +2804,14 @@ constexpr uint64_t kStatsTag = 0x57A7500D0000000Full;
 unsigned long long* device_stats(omf_plan* p, hipStream_t st) {
   bool fresh = false;
   uint64_t* host = nullptr;
-  void* d = omf_plan_access::topk_table(p, kStatsTag, 64, &fresh, &host);
+  void* d = topk_table(p, kStatsTag, 64, &fresh, &host);
   if (!d) return nullptr;
   if (fresh && hipMemsetAsync(d, 0, 64, st) != hipSuccess) return nullptr;
   return static_cast<unsigned long long*>(d);
 }
 
 int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uint32_t* status, SetupTable* out) {
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(p);
+  const std::vector<int64_t>& sizes = p->sizes;
   const int32_t nt = (int32_t)sizes.size();
   std::vector<uint32_t> smap;
   for (int32_t t = 0; t < nt; ++t) {  // sampling blocks: as sample_stride on the device
@@ -2883,7 +2863,7 @@ int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uin
   uint64_t key;
   std::memcpy(&key, &ratio, 8);
   key ^= kSetupTag ^ ((uint64_t)max_runs * 0x9E3779B97F4A7C15ull);
-  uint8_t* d = static_cast<uint8_t*>(omf_plan_access::topk_table(p, key, o, &fresh, &host));
+  uint8_t* d = static_cast<uint8_t*>(topk_table(p, key, o, &fresh, &host));
   if (!d) return fail(OMF_ENOMEM, "omf_topk_encode: table allocation failed");
   out->kk = reinterpret_cast<int64_t*>(d + o_kk);
   out->koff = reinterpret_cast<int64_t*>(d + o_koff);
@@ -2907,7 +2887,7 @@ int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uin
     OMF_HIP(hipMemcpyAsync(out->supinfo, supinfo.data(), 4 * supinfo.size(), hipMemcpyHostToDevice, st));
     if (!zmap.empty())
       OMF_HIP(hipMemcpyAsync(out->zmap, zmap.data(), 4 * zmap.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(topk_setup, dim3(1), dim3(kThreads), 0, st, omf_plan_access::d_sizes(p), nt, ratio, out->kk,
+    hipLaunchKernelGGL(topk_setup, dim3(1), dim3(kThreads), 0, st, p->d_sizes, nt, ratio, out->kk,
                        out->koff, out->tfirst, out->tlast, out->bbase, out->kb2, out->sbase, status, 0u);
     OMF_HIP(hipGetLastError());
     OMF_HIP(hipStreamSynchronize(st));  // once per (plan, ratio): the host copy of smap is freed on return
@@ -2930,7 +2910,7 @@ int omf_plan_set_topk(omf_plan* plan, int32_t groups, int32_t force_fallback, in
   if (sample_runs > 0 && (sample_runs < 64 || sample_runs > (1 << 20)))
     return fail(OMF_EINVAL, "omf_plan_set_topk: sample_runs must be 0 (default) or in [64, 2^20]");
   (void)knobs(plan);  // the environment's values first, so a negative argument keeps them
-  TopkKnobs& k = omf_plan_access::topk_knobs(plan);
+  TopkKnobs& k = plan->topk_knobs;
   if (groups >= 1) k.groups = groups;
   if (force_fallback > 2) return fail(OMF_EINVAL, "omf_plan_set_topk: force_fallback must be 0, 1 or 2");
   if (force_fallback >= 0) k.force_fallback = force_fallback;
@@ -2942,13 +2922,13 @@ int omf_plan_set_topk(omf_plan* plan, int32_t groups, int32_t force_fallback, in
 
 int omf_topk_stats(omf_plan* plan, int64_t* out6, int32_t reset) {
   if (!plan || !out6) return fail(OMF_EINVAL, "plan and out6 must be non-NULL");
-  TopkStats& s = omf_plan_access::topk_knobs(plan).stats;
-  DeviceGuard g(omf_plan_access::device(plan));
+  TopkStats& s = plan->topk_knobs.stats;
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   OMF_HIP(hipDeviceSynchronize());  // the device keeps the path counters (the exact tail's)
   bool fresh = false;
   uint64_t* host = nullptr;
-  void* d = omf_plan_access::topk_table(plan, kStatsTag, 64, &fresh, &host);
+  void* d = topk_table(plan, kStatsTag, 64, &fresh, &host);
   if (!d) return fail(OMF_ENOMEM, "omf_topk_stats: counter table allocation failed");
   unsigned long long dv[4] = {0, 0, 0, 0};
   if (fresh) OMF_HIP(hipMemset(d, 0, 64));
@@ -2975,7 +2955,7 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
   if (residual_mode < 0 || residual_mode > 2 || (residual_mode != 0 && !residual))
     return fail(OMF_EINVAL, "residual_mode must be 0 (none), 1 (compensate+update) or 2 (init) with a residual buffer");
   if (!(ratio == ratio)) return fail(OMF_EINVAL, "ratio is NaN");
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(plan);
+  const std::vector<int64_t>& sizes = plan->sizes;
   int64_t kmax = 0;
   for (int64_t n : sizes) {
     const int64_t k = omf_topk_k(n, ratio);
@@ -2983,12 +2963,12 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
     if (n > 0x7fffffffLL) return fail(OMF_EINVAL, "tensor too large for 32-bit candidate indices");
     kmax = std::max(kmax, k);
   }
-  if (omf_plan_access::arena_end(plan) > 0xffffffffLL) return fail(OMF_EINVAL, "arena too large for the sort");
+  if (plan->arena_end > 0xffffffffLL) return fail(OMF_EINVAL, "arena too large for the sort");
   if (((uintptr_t)x & 15) || (residual && ((uintptr_t)residual & 15)))
     return fail(OMF_EINVAL, "x and residual must be 16-byte aligned");
   const WsLayout L = layout(plan);
   if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
   uint8_t* w = static_cast<uint8_t*>(ws);
@@ -3024,11 +3004,11 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
   uint32_t* bstart = reinterpret_cast<uint32_t*>(w + L.bstart);
   BucketRec* brec = reinterpret_cast<BucketRec*>(w + L.brec);
   uint32_t* bfill = reinterpret_cast<uint32_t*>(w + L.bfill);
-  const int32_t nt = omf_plan_access::ntensors(plan);
-  int64_t n_items = 0;
-  const Item* items = static_cast<const Item*>(omf_plan_access::flat_items(plan, &n_items));
-  const int64_t* d_sizes = omf_plan_access::d_sizes(plan);
-  const int64_t* d_begins = omf_plan_access::d_begins(plan);
+  const int32_t nt = plan->nt;
+  const int64_t n_items = plan->n_flat;
+  const Item* items = plan->d_flat;
+  const int64_t* d_sizes = plan->d_sizes;
+  const int64_t* d_begins = plan->d_begins;
   // t' lives in the residual (EF modes) or is alpha * x (mode 0)
   const float* tp = residual_mode == 0 ? x : residual;
   const float scale = residual_mode == 0 ? alpha : 1.0f;
@@ -3037,12 +3017,12 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
 
   const bool glob = global_path(plan);
   if (!glob) OMF_HIP(hipMemsetAsync(w, 0, L.zero_end, st));
-  HostSync* hsync = host_sync(omf_plan_access::device(plan));
+  HostSync* hsync = host_sync(plan->device);
   if (!hsync) return fail(OMF_EHIP, "omf_topk_encode: device index out of range");
   // the per-(plan, ratio) constant tables: made by topk_setup on the first call at this ratio
   SetupTable tb;
   const TopkKnobs& kn = knobs(plan);
-  TopkStats& stats = omf_plan_access::topk_knobs(plan).stats;
+  TopkStats& stats = plan->topk_knobs.stats;
   const int64_t max_runs = sample_max_runs(kn);
   const float2 sure_zc = sure_margin(kn);
   if (int r = setup_table(plan, ratio, max_runs, st, status, &tb)) return r;
@@ -3052,7 +3032,7 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
     unsigned long long* dstats = device_stats(plan, st);
     if (!dstats) return fail(OMF_ENOMEM, "omf_topk_encode: counter table allocation failed");
     const bool forced = kn.force_fallback != 0;
-    const std::vector<Group> groups = make_groups(omf_plan_access::sizes(plan), ratio, max_runs,
+    const std::vector<Group> groups = make_groups(plan->sizes, ratio, max_runs,
                                                   topk_group_count(plan, kn));
     if (groups.size() > 1)
       if (int r = pipe_streams(hsync)) return r;
@@ -3158,12 +3138,12 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
     ta.values = values;
     ta.indices = indices;
     ta.stats = dstats;
-    ta.err = omf_plan_access::err_word(plan);
+    ta.err = plan->err_word();
     ta.zmap = (const uint2*)tb.zmap;
     ta.nzc = (uint32_t)tb.nzb;
     ta.zcnt = zcnt;
     ta.tsize = d_sizes;
-    hipLaunchKernelGGL(topk_exact_tail, dim3(tail_grid(omf_plan_access::device(plan))), dim3(kThreads), 0, st, ta);
+    hipLaunchKernelGGL(topk_exact_tail, dim3(tail_grid(plan->device)), dim3(kThreads), 0, st, ta);
     OMF_HIP(hipGetLastError());
     (void)tmp_bytes;
     return OMF_OK;
@@ -3181,7 +3161,7 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
                        seg_b, seg_e);
     OMF_HIP(hipGetLastError());
     OMF_HIP(rocprim::segmented_radix_sort_keys_desc(w + L.tmp, tmp_bytes, cand, sorted,
-                                                    (unsigned int)omf_plan_access::arena_end(plan), (unsigned int)nt,
+                                                    (unsigned int)plan->arena_end, (unsigned int)nt,
                                                     seg_b, seg_e, 0, 64, st, false));
   }
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((kmax + kThreads - 1) / kThreads, 1024));
@@ -3358,8 +3338,8 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   if (residual_mode < 0 || residual_mode > 2 || (residual_mode != 0 && !residual) || (residual_mode == 0 && !x))
     return fail(OMF_EINVAL, "residual_mode 0 needs x, modes 1 / 2 the residual the encode updated");
   if (!(ratio == ratio)) return fail(OMF_EINVAL, "ratio is NaN");
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(plan);
-  const std::vector<int64_t>& offsets = omf_plan_access::offsets(plan);
+  const std::vector<int64_t>& sizes = plan->sizes;
+  const std::vector<int64_t>& offsets = plan->offsets;
   const int32_t nt = (int32_t)sizes.size();
   std::vector<int64_t> K(nt + 1, 0);
   for (int32_t t = 0; t < nt; ++t) {
@@ -3371,7 +3351,7 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
   if (n_reordered) *n_reordered = 0;
   if (nt == 0) return OMF_OK;
-  const int dev = omf_plan_access::device(plan);
+  const int dev = plan->device;
   DeviceGuard g(dev);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
@@ -3381,8 +3361,8 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   SetupTable tb;
   if (int r = setup_table(plan, ratio, sample_max_runs(knobs(plan)), st, reinterpret_cast<uint32_t*>(w + L.status), &tb))
     return r;
-  int64_t n_items = 0;
-  const Item* items = static_cast<const Item*>(omf_plan_access::flat_items(plan, &n_items));
+  const int64_t n_items = plan->n_flat;
+  const Item* items = plan->d_flat;
   const bool ef = residual_mode != 0;
   OMF_HIP(hipMemsetAsync(cnt, 0, 4 * (size_t)nt, st));
   if (n_items > 0) {
@@ -3394,7 +3374,7 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
                          tb.koff, values, cnt);
   }
   hipLaunchKernelGGL(topk_tie_flags, dim3((unsigned)nt), dim3(kThreads), 0, st, tb.kk, tb.koff,
-                     omf_plan_access::d_sizes(plan), values, cnt, ef ? 1 : 0, flags);
+                     plan->d_sizes, values, cnt, ef ? 1 : 0, flags);
   OMF_HIP(hipGetLastError());
   std::vector<uint32_t> hflags(nt);
   OMF_HIP(hipMemcpyAsync(hflags.data(), flags, 4 * (size_t)nt, hipMemcpyDeviceToHost, st));
@@ -3453,7 +3433,7 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   return OMF_OK;
 }
 
-// Whole-arena decode.  Plan-owned constant tables per selection layout (omf_plan_access::
+// Whole-arena decode.  Plan-owned constant tables per selection layout (omf_plan.h 
 // topk_table, keyed by the ratio; topk_table_counts, keyed by a received message's per-tensor
 // counts): koff[nt + 1] (int64: each tensor's first value), cap_base[nsuper + 1] (uint32: the
 // tiled decode's bucket-capacity prefix) and blk_t (per place block: its first and last tensor).
@@ -3469,7 +3449,7 @@ struct DecTables {
 
 // k_t of every tensor at `ratio` (omf_topk_k); false when some k_t > n_t.
 static bool ratio_counts(const omf_plan* plan, double ratio, std::vector<int64_t>& ks) {
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(plan);
+  const std::vector<int64_t>& sizes = plan->sizes;
   ks.resize(sizes.size());
   for (size_t t = 0; t < sizes.size(); ++t) {
     ks[t] = omf_topk_k(sizes[t], ratio);
@@ -3482,7 +3462,7 @@ static bool ratio_counts(const omf_plan* plan, double ratio, std::vector<int64_t
 // has elements would need duplicates; the caller decodes such a layer on its own).
 static int check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot) {
   if (!counts) return fail(OMF_EINVAL, "counts is NULL");
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(plan);
+  const std::vector<int64_t>& sizes = plan->sizes;
   int64_t s = 0;
   for (size_t t = 0; t < sizes.size(); ++t) {
     if (counts[t] < 0 || counts[t] > sizes[t])
@@ -3499,13 +3479,13 @@ static int64_t dec_place_blocks(int64_t ktot) { return std::max<int64_t>(1, (kto
 
 static void dec_tables_host(const omf_plan* p, const int64_t* ks, std::vector<int64_t>& koff,
                             std::vector<uint32_t>& cap_base, int32_t& nsuper, std::vector<uint32_t>* blk_t = nullptr) {
-  const std::vector<int64_t>& sizes = omf_plan_access::sizes(p);
+  const std::vector<int64_t>& sizes = p->sizes;
   const int32_t nt = (int32_t)sizes.size();
-  const int64_t ae = omf_plan_access::arena_end(p);
+  const int64_t ae = p->arena_end;
   nsuper = (int32_t)((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits);
   koff.assign((size_t)nt + 1, 0);
   std::vector<double> expect((size_t)nsuper, 0.0);
-  const std::vector<int64_t>& begins = omf_plan_access::offsets(p);
+  const std::vector<int64_t>& begins = p->offsets;
   for (int32_t t = 0; t < nt; ++t) {
     const int64_t n = sizes[t], k = ks[t];
     koff[(size_t)t + 1] = koff[(size_t)t] + k;
@@ -3559,16 +3539,16 @@ static uint64_t ratio_key(double ratio) {
 // The plan's tables for the layout ks (computed and uploaded on first use; the bucket total is
 // kept in the table's host word).  ratio != NULL: keyed by the ratio, else by the counts.
 static int dec_tables(omf_plan* p, const int64_t* ks, int64_t ktot, const double* ratio, DecTables* out) {
-  const int32_t nt = omf_plan_access::ntensors(p);
-  const int64_t ae = omf_plan_access::arena_end(p);
+  const int32_t nt = p->nt;
+  const int64_t ae = p->arena_end;
   const int32_t nsuper = (int32_t)((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits);
   const int64_t nb = dec_place_blocks(ktot);
   const size_t o_cap = align256(8 * ((size_t)nt + 1)), o_blk = o_cap + align256(4 * ((size_t)nsuper + 1));
   const size_t bytes = o_blk + 8 * (size_t)nb;
   bool fresh = false;
   uint64_t* host = nullptr;
-  void* d = ratio ? omf_plan_access::topk_table(p, ratio_key(*ratio), bytes, &fresh, &host)
-                  : omf_plan_access::topk_table_counts(p, ks, bytes, &fresh, &host);
+  void* d = ratio ? topk_table(p, ratio_key(*ratio), bytes, &fresh, &host)
+                  : topk_table_counts(p, ks, bytes, &fresh, &host);
   if (!d) return fail(OMF_ENOMEM, "Top-K decode: table allocation failed");
   out->koff = static_cast<int64_t*>(d);
   out->cap_base = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d) + o_cap);
@@ -3601,12 +3581,12 @@ static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const 
                          const int64_t* indices, float* y, int32_t mode, void* ws, size_t ws_bytes, void* stream) {
   if (mode < 0 || mode > 2) return fail(OMF_EINVAL, "Top-K arena decode: mode must be 0, 1 or 2");
   if ((ktot && (!values || !indices)) || !y) return fail(OMF_EINVAL, "Top-K arena decode: NULL buffer");
-  const int32_t nt = omf_plan_access::ntensors(plan);
+  const int32_t nt = plan->nt;
   if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "Top-K arena decode: too many tensors (decode per tensor)");
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t ae = omf_plan_access::arena_end(plan);
+  const int64_t ae = plan->arena_end;
   DecTables tb;
   if (int r = dec_tables(plan, ks, ktot, ratio, &tb)) return r;
   if (mode == 0 && ws && ((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits) <= kDecMaxSuper) {
@@ -3625,7 +3605,7 @@ static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const 
     if (ktot > 0) {
       const dim3 gb((unsigned)dec_place_blocks(ktot));
       hipLaunchKernelGGL(topk_dec_place, gb, dim3(kThreads), 4 * (size_t)tb.nsuper, st, values, indices,
-                         omf_plan_access::d_sizes(plan), omf_plan_access::d_begins(plan), (const int64_t*)tb.koff,
+                         plan->d_sizes, plan->d_begins, (const int64_t*)tb.koff,
                          (const uint32_t*)tb.blk_t, ktot, (const uint32_t*)tb.cap_base, fill, pairs, ovf_cnt, ovf);
     }
     hipLaunchKernelGGL(topk_dec_tiles, dim3((unsigned)tb.nsuper), dim3(kDecTileThreads), 0, st, (const uint64_t*)pairs,
@@ -3638,7 +3618,7 @@ static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const 
   if (ktot == 0) return OMF_OK;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 4096));
   hipLaunchKernelGGL(topk_scatter_arena, dim3(gx), dim3(kThreads), 0, st, values, indices,
-                     omf_plan_access::d_sizes(plan), omf_plan_access::d_begins(plan), (const int64_t*)tb.koff, (int)nt,
+                     plan->d_sizes, plan->d_begins, (const int64_t*)tb.koff, (int)nt,
                      ktot, y, mode == 2 ? 1 : 0);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
@@ -3691,9 +3671,9 @@ int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indic
   int64_t ktot = 0;
   if (int r = check_counts(plan, counts, &ktot)) return r;
   if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_indices: indices is NULL");
-  const int32_t nt = omf_plan_access::ntensors(plan);
+  const int32_t nt = plan->nt;
   if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_indices: too many tensors");
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
   DecTables tb;
@@ -3701,7 +3681,7 @@ int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indic
   OMF_HIP(hipMemsetAsync(bad, 0x7f, 4, st));  // 0x7f7f7f7f: no tensor
   if (ktot == 0) return OMF_OK;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + 4 * kThreads - 1) / (4 * kThreads), 2048));
-  hipLaunchKernelGGL(topk_check_idx, dim3(gx), dim3(kThreads), 0, st, indices, omf_plan_access::d_sizes(plan),
+  hipLaunchKernelGGL(topk_check_idx, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
                      (const int64_t*)tb.koff, (int)nt, ktot, bad);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
@@ -3714,9 +3694,9 @@ int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64
   int64_t ktot = 0;
   if (int r = check_counts(plan, counts, &ktot)) return r;
   if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_duplicates: indices is NULL");
-  const int32_t nt = omf_plan_access::ntensors(plan);
+  const int32_t nt = plan->nt;
   if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_duplicates: too many tensors");
-  DeviceGuard g(omf_plan_access::device(plan));
+  DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
   OMF_HIP(hipMemsetAsync(flags, 0, 4 * (size_t)nt, st));
@@ -3725,21 +3705,21 @@ int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64
   if (int r = dec_tables(plan, counts, ktot, nullptr, &tb)) return r;
   // the bitmap is the plan's: a call on another stream than the plan's previous stateful launch
   // is ordered after it (include/omf_codec.h), so two checks never mark and clear it at once
-  if (int r = omf_plan_access::order_enter(plan, st)) return r;
+  if (int r = plan_enter(plan, st)) return r;
   constexpr uint64_t kDupTag = 0xD0B1E5B17A9E0000ull;
-  const size_t words = (size_t)((omf_plan_access::arena_end(plan) + 31) / 32);
+  const size_t words = (size_t)((plan->arena_end + 31) / 32);
   bool fresh = false;
   uint64_t* host = nullptr;
-  uint32_t* bits = static_cast<uint32_t*>(omf_plan_access::topk_table(plan, kDupTag, 4 * words, &fresh, &host));
+  uint32_t* bits = static_cast<uint32_t*>(topk_table(plan, kDupTag, 4 * words, &fresh, &host));
   if (!bits) return fail(OMF_ENOMEM, "omf_topk_check_duplicates: bitmap allocation failed");
   if (fresh) OMF_HIP(hipMemsetAsync(bits, 0, 4 * words, st));
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 2048));
-  hipLaunchKernelGGL(topk_dup_bits<true>, dim3(gx), dim3(kThreads), 0, st, indices, omf_plan_access::d_sizes(plan),
-                     omf_plan_access::d_begins(plan), (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
-  hipLaunchKernelGGL(topk_dup_bits<false>, dim3(gx), dim3(kThreads), 0, st, indices, omf_plan_access::d_sizes(plan),
-                     omf_plan_access::d_begins(plan), (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
+  hipLaunchKernelGGL(topk_dup_bits<true>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
+                     plan->d_begins, (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
+  hipLaunchKernelGGL(topk_dup_bits<false>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
+                     plan->d_begins, (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
   OMF_HIP(hipGetLastError());
-  return omf_plan_access::order_leave(plan, st);
+  return plan_leave(plan, st);
 }
 
 int omf_topk_decode(const float* values, const int64_t* indices, int64_t k, float* y, int64_t n, int32_t mode,
