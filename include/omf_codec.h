@@ -177,6 +177,9 @@ int omf_qsgd_norms_ex(omf_plan* plan, const float* x, float alpha, int32_t value
  * strategies run divide + encode.  Arguments after avg_out as omf_qsgd_encode (no alpha,
  * no norm_in).  avg_out must be disjoint from acc for the one-launch paths; avg_out == acc
  * is accepted and runs as divide (in place) + encode; a partial overlap is OMF_EINVAL.
+ * Only the tensors' elements of avg_out are written (the padding between them keeps its bytes,
+ * in place too), and a zero keeps IEEE's sign (-0.0 / 3 is -0.0).  The same holds for acc_out and
+ * avg_out of omf_ps_accumulate_apply_encode.
  */
 int omf_ps_apply_encode(omf_plan* plan, const float* acc, float divisor, float* avg_out, int32_t bit_width,
                         const float* u, uint64_t seed, uint64_t offset, void* q_out, float* norm_out, void* stream);
@@ -216,7 +219,11 @@ int omf_qsgd_decode(omf_plan* plan, const void* q, int32_t width, int32_t levels
  * elem_end) only (every element of those blocks is written, so the payload of those whole blocks
  * must be in place).  Lets a caller decode an arena chunk by chunk as its payload arrives and
  * copy each decoded chunk out while the next is staged (the CPU placement of
- * decode_updates_dict, global_grpc_compression.py:214-223).  Same results as one full decode. */
+ * decode_updates_dict, global_grpc_compression.py:214-223).  Same results as one full decode.
+ * An empty range (elem_end == elem_begin, at any position) overlaps no block: nothing is launched
+ * and nothing is written, with accumulate too.  The part of a range past arena_end is ignored;
+ * elem_begin < 0 or elem_end < elem_begin is OMF_EINVAL.  An arena of fewer than 4 elements is one
+ * block: any non-empty range decodes it whole. */
 int omf_qsgd_decode_range(omf_plan* plan, const void* q, int32_t width, int32_t levels, const float* norm,
                           float* y_out, int32_t accumulate, int64_t elem_begin, int64_t elem_end, void* stream);
 

@@ -186,6 +186,8 @@ __device__ __forceinline__ float4 u24x4(uint32_t w0, uint32_t w1, uint32_t w2) {
 // q within 1 ulp, the second fma-corrected step rounds correctly).  Valid for d in
 // [2^-100, 2^100] and |x| >= 2^-96 or x == 0; callers take x / d elsewhere
 // (scripts/exp/div_check.c: 0 mismatches in 1e9 random and near-halfway cases).
+// A zero's quotient is a zero whose sign is not IEEE's: the correction steps add +0, so
+// -0 / d with d > 0 gives +0.  A caller that stores the quotient fixes the sign itself.
 __device__ __forceinline__ float div_markstein(float x, float d, float r) {
   float q = __fmul_rn(x, r);
   float e = fmaf(-q, d, x);

@@ -29,7 +29,9 @@
 //                          registers across one grid-wide barrier.
 //   qsgd_decode_arena      y = (norm * q) / L over the arena's 4 Ki blocks, optionally accumulated (PS);
 //   qsgd_decode_flat       the same per flat item with byte loads: payloads of fewer than 4 elements.
-//   div_f32_kernel         y /= d (the in-place PS step).
+//   div_f32_kernel         y /= d over a flat buffer (omf_div_f32).
+//   items_f32_kernel       dst = src / d or src over the tensors' elements only (the in-place PS step,
+//                          the last client's two-call fallback): arena padding is never written.
 //
 // Host side (the end of the file): omf_plan_create / upload_plan carve the plan's device block from
 // the tables of omf_plan_layout.cpp; encode_launch asks choose_encoder (omf_plan_layout.h) which
@@ -1762,6 +1764,23 @@ __global__ __launch_bounds__(kThreads) void div_f32_kernel(float* __restrict__ y
   }
 }
 
+// dst = src / d (DIV) or src over the plan's flat items: the tensors' elements only, so the padding
+// between tensors is neither read nor written.  dst may be src.  Item starts are multiples of 4.
+template <bool DIV>
+__global__ __launch_bounds__(kThreads) void items_f32_kernel(const Item* __restrict__ items, const float* src, float* dst,
+                                                             float d) {
+  const Item it = items[blockIdx.x];
+  for (int64_t e = it.begin + 4 * (int64_t)threadIdx.x; e < it.end; e += 4 * kThreads) {
+    if (e + 4 <= it.end) {
+      float4 v = *reinterpret_cast<const float4*>(src + e);
+      if (DIV) { v.x = v.x / d; v.y = v.y / d; v.z = v.z / d; v.w = v.w / d; }
+      *reinterpret_cast<float4*>(dst + e) = v;
+    } else {
+      for (int64_t i = e; i < it.end; ++i) dst[i] = DIV ? src[i] / d : src[i];
+    }
+  }
+}
+
 }  // namespace
 
 // ====================================================================== host side
@@ -2523,12 +2542,15 @@ int omf_ps_apply_encode(omf_plan* p, const float* acc, float divisor, float* avg
   if (!alias)  // one ring launch: read acc once, write avg and the payload
     return encode_impl(p, acc, 1.0f, bit_width, u, seed, offset, nullptr, q_out, norm_out, false, stream, divisor,
                        avg_out);
-  // in place: the same results as divide, then encode
+  // in place: the same results as divide, then encode (the tensors' elements only: the padding
+  // between them stays as the caller left it)
   DeviceGuard g(p->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  if (avg_out != acc)
-    OMF_HIP(hipMemcpyAsync(avg_out, acc, 4 * (size_t)p->arena_end, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (int r = omf_div_f32(avg_out, p->arena_end, divisor, stream)) return r;
+  if (p->n_flat > 0) {
+    hipLaunchKernelGGL(items_f32_kernel<true>, dim3((unsigned)p->n_flat), dim3(kThreads), 0, (hipStream_t)stream,
+                       (const Item*)p->d_flat, (const float*)avg_out, avg_out, divisor);
+    OMF_HIP(hipGetLastError());
+  }
   return encode_impl(p, avg_out, 1.0f, bit_width, u, seed, offset, nullptr, q_out, norm_out, false, stream);
 }
 
@@ -2565,7 +2587,11 @@ int omf_ps_accumulate_apply_encode(omf_plan* p, const float* acc, const void* q_
   }
   // other encoders: the decoder's accumulate, then the fused step (the same bytes)
   float* sum = acc_out ? acc_out : avg_out;
-  if (sum != acc) OMF_HIP(hipMemcpyAsync(sum, acc, bytes, hipMemcpyDeviceToDevice, st));
+  if (sum != acc && p->n_flat > 0) {  // the tensors' elements only: sum's padding is not written
+    hipLaunchKernelGGL(items_f32_kernel<false>, dim3((unsigned)p->n_flat), dim3(kThreads), 0, st, (const Item*)p->d_flat,
+                       acc, sum, 1.0f);
+    OMF_HIP(hipGetLastError());
+  }
   if (int r = omf_qsgd_decode(p, q_in, width_in, levels_in, norm_in, sum, 1, stream)) return r;
   return omf_ps_apply_encode(p, sum, divisor, avg_out, bit_width, u, seed, offset, q_out, norm_out, stream);
 }
@@ -2633,8 +2659,9 @@ int omf_qsgd_decode_range(omf_plan* p, const void* q, int32_t width, int32_t lev
                           int32_t accumulate, int64_t elem_begin, int64_t elem_end, void* stream) {
   if (!p) return fail(OMF_EINVAL, "plan is NULL");
   if (elem_begin < 0 || elem_end < elem_begin) return fail(OMF_EINVAL, "omf_qsgd_decode_range: bad element range");
-  if (p->arena_end < 4)  // the item decoder of tiny payloads has no block ranges: decode it all
-    return decode_blocks(p, q, width, levels, norm, y, accumulate, 0, p->n_dec_blocks, stream);
+  if (elem_end == elem_begin) return OMF_OK;  // an empty range overlaps no block, wherever it lies
+  if (p->arena_end < 4)  // the item decoder of tiny payloads has no block ranges: its one block, whole
+    return decode_blocks(p, q, width, levels, norm, y, accumulate, 0, elem_begin < kDecBlk ? p->n_dec_blocks : 0, stream);
   return decode_blocks(p, q, width, levels, norm, y, accumulate, elem_begin / kDecBlk,
                        (elem_end + kDecBlk - 1) / kDecBlk, stream);
 }

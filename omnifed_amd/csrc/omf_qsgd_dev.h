@@ -76,14 +76,20 @@ struct Divisor {
     const f32x2_t lo = div2_markstein((f32x2_t){x.x, x.y}, D, R);
     const f32x2_t hi = div2_markstein((f32x2_t){x.z, x.w}, D, R);
     float4 q = make_float4(lo.x, lo.y, hi.x, hi.y);
-    // Quad pre-test (v_min3 with |.| modifiers): min |x| < 2^-96 catches every tiny input
-    // (and zeros, which Markstein divides exactly anyway); only then the per-element test.
+    // Quad pre-test (v_min3 with |.| modifiers): min |x| < 2^-96 catches every tiny input and
+    // every zero; only then the per-element test.  Markstein's quotient of a zero is a zero, but
+    // its correction steps add +0 to it, so -0 / d (d > 0) would come out +0: a zero takes the
+    // sign of x * (1 / d), the IEEE quotient's (the fused PS step stores this quotient).
     const float mn = fminf(fminf(fabsf(x.x), fabsf(x.y)), fminf(fabsf(x.z), fabsf(x.w)));
     if (__any(mn < 0x1p-96f)) {  // wave-uniform branch: tiny inputs take the exact division
       if (div_tiny(x.x)) q.x = x.x / d;
       if (div_tiny(x.y)) q.y = x.y / d;
       if (div_tiny(x.z)) q.z = x.z / d;
       if (div_tiny(x.w)) q.w = x.w / d;
+      if (x.x == 0.0f) q.x = __fmul_rn(x.x, r);
+      if (x.y == 0.0f) q.y = __fmul_rn(x.y, r);
+      if (x.z == 0.0f) q.z = __fmul_rn(x.z, r);
+      if (x.w == 0.0f) q.w = __fmul_rn(x.w, r);
     }
     return q;
   }
