@@ -270,6 +270,15 @@ int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t level
  *   [K_t, K_t + k_t) with K_t = sum_{u<t} k_u (packed in plan order).
  * Order within a tensor: descending |t'|, ties by ascending index (torch.topk's
  * order for k*64 <= n on the reference CPU path; ties there are unspecified).
+ * |t'| is compared as the unsigned integer bits(t') & 0x7fffffff, so a NaN ranks above
+ * inf (torch.topk ranks NaN first too), NaNs of one payload tie like any equal
+ * magnitudes, and +0 ties with -0.  A selected slot's residual t' - t' is +0 for a
+ * finite t'; a NaN t' leaves itself, and an infinite one the quiet NaN 0xffc00000 (IEEE 754
+ * leaves the sign of inf - inf's NaN to the platform: gfx950 sets it, as the x86 hosts
+ * of the reference do; every path here writes that one NaN, the host rewrite of
+ * omf_topk_torch_order included).  Only the tensors' elements of the residual are read
+ * or written; x and the padding of both arenas are never written, and padding is never
+ * read as data.  values / indices are written over [0, K) only.
  * ws: caller workspace of omf_topk_workspace_bytes(plan, ratio) bytes.
  * Stream-asynchronous: the plan kernel's verdict is read by the launches queued behind it (the
  * bucket kernels, the zero fill and the exact tail, each leaving at once when the verdict does

@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <bit>
 #include <chrono>
 #include <memory>
 #include <mutex>
@@ -3315,7 +3316,13 @@ int reorder_tensor(hipStream_t s, const float* src, float* residual, bool ef, fl
     same_set = a == b;
   }
   if (!same_set) {  // the residual: t' with torch's selection zeroed (t' - t')
-    for (int64_t j = 0; j < k; ++j) tp[sel[j]] = tp[sel[j]] - tp[sel[j]];
+    // (spelled out, not t' - t': omf_codec.h promises the device's NaN for an infinite t' whichever
+    // path wrote the slot, and the sign of inf - inf's NaN is the host platform's)
+    const float inf_nan = std::bit_cast<float>(0xffc00000u);
+    for (int64_t j = 0; j < k; ++j) {
+      float& e = tp[sel[j]];
+      e = std::isfinite(e) ? 0.0f : std::isnan(e) ? e : inf_nan;
+    }
     if (!hip(hipMemcpyAsync(residual + off, tp.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s), "residual to device"))
       return OMF_EHIP;
   }

@@ -20,5 +20,13 @@ from .qsgd import (  # noqa: F401
     storage_width,
 )
 from .philox import philox4x32_10, philox_uniforms  # noqa: F401
-from .topk import TopKOracle, topk_k, topk_sparse, topk_desparse  # noqa: F401
+from .topk import (  # noqa: F401
+    TopKOracle,
+    mag_keys,
+    topk_desparse,
+    topk_ef_step,
+    topk_k,
+    topk_select_index_order,
+    topk_sparse,
+)
 from .aggregate import ps_aggregate, layerwise_decompress  # noqa: F401

@@ -6,6 +6,7 @@ import torch
 
 import oracle
 from inputs import exact_input
+from topk_matrix_inputs import _sample_positions
 from omnifed_amd import codec
 from omnifed_amd.hybrid.communicator import global_grpc_pb2 as pb
 from omnifed_amd.hybrid.communicator.global_grpc_compression import (
@@ -102,28 +103,6 @@ def test_topk_degenerate_ties(gpu):
     rest = sorted(set(ih.tolist()) - set(nz.tolist()))
     assert rest == sorted(set(range(n)) - set(nz.tolist()))[: k - len(nz)]
     assert set(oi.tolist()) != set(ih.tolist())  # the two rules differ on this input
-
-
-def _fmix32(h):
-    h = h.astype(np.uint64)
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
-    return h ^ (h >> np.uint64(16))
-
-
-def _sample_positions(n, t, max_runs):
-    """The elements omf_topk.hip's topk_sample reads for tensor t: one aligned run of 16 per
-    max(256, ceil(n / max_runs)) elements, at a hashed position."""
-    stride = max(256, -(-n // max_runs))
-    lo = np.arange(0, n, stride, dtype=np.uint64)
-    key = lo ^ np.uint64((t * 0x9E3779B9) & 0xFFFFFFFF)
-    span = np.minimum(np.uint64(stride), np.uint64(n) - lo)
-    runs = np.maximum(np.uint64(1), span // np.uint64(16))
-    start = (lo + np.uint64(16) * (_fmix32(key) % runs)).astype(np.int64)
-    pos = (start[:, None] + np.arange(16)[None, :]).reshape(-1)
-    return pos[pos < n]
 
 
 @pytest.mark.parametrize("alpha", [1.0, 3.0])
