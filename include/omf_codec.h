@@ -64,7 +64,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 112
+#define OMF_ABI_VERSION 113
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -232,6 +232,31 @@ int omf_qsgd_decode_range(omf_plan* plan, const void* q, int32_t width, int32_t 
  * CentralServerServicer._apply_model_updates, global_grpc_server.py:155-171).
  */
 int omf_div_f32(float* y, int64_t n, float divisor, void* stream);
+
+/*
+ * K clients' QSGD payloads decoded, summed and averaged in ONE pass over the arena: the PS's
+ * acc[name] += update per client followed by acc / total_samples
+ * (CentralServerServicer._accumulate_model_updates and _apply_model_updates,
+ * src/omnifed/hybrid/communicator/global_grpc_server.py:147-171), without the accumulator's
+ * round trip through memory per client.  Per element i of tensor t:
+ *   s_0 = init ? y_out_i : +0
+ *   s_k = fl32(s_{k-1} + fl32(fl32(norm[k-1][t] * q[k-1]_i) / fl32(levels)))   k = 1..nclients, in array order
+ *   y_out_i = divisor != 0 ? fl32(s_K / divisor) : s_K
+ * q / norm: HOST arrays of nclients DEVICE pointers, read at the call (the pointers travel as
+ * kernel arguments: nothing is uploaded, so the call may be captured into a HIP graph); each q[k]
+ * a payload arena as omf_qsgd_encode writes it, each norm[k] ntensors fp32 (0 for a tensor absent
+ * from that client's message).  One (width, levels) for all clients of a call, as omf_qsgd_decode.
+ * init == 0: y_out is not read, and every padding element of [0, arena_end) is written too
+ * (fl32(+0 / divisor), or +0 without a divisor), so the arena holds, byte for byte, what
+ * hipMemset(y_out, 0), nclients x omf_qsgd_decode(accumulate=1) in order and
+ * omf_div_f32(y_out, arena_end, divisor) leave (a lone client's -0 term gives +0).
+ * init != 0: the sum starts from y_out; padding keeps its bytes, with or without a divisor.
+ * Any nclients >= 1: at most 8 clients go into one launch, more are chained (same bytes).
+ * OMF_EINVAL: nclients < 1, a NULL entry in q or norm, a bad width or levels, a misaligned buffer
+ * (as omf_qsgd_decode), y_out overlapping a payload or norm buffer.
+ */
+int omf_qsgd_decode_sum(omf_plan* plan, const void* const* q, const float* const* norm, int32_t nclients,
+                        int32_t width, int32_t levels, float* y_out, int32_t init, float divisor, void* stream);
 
 /*
  * Opt-in bit-packed QSGD wire (NOT reference-compatible, a new

@@ -62,6 +62,8 @@ SIGNATURES = {
     "omf_qsgd_decode": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_p]),
     "omf_qsgd_decode_range": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i64, _c_i64, _c_p]),
     "omf_div_f32": (ctypes.c_int, [_c_p, _c_i64, _c_f32, _c_p]),
+    "omf_qsgd_decode_sum": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32, _c_i32,
+                                           _c_p, _c_i32, _c_f32, _c_p]),
     "omf_qsgd_packed_bits": (_c_i32, [_c_i32]),
     "omf_qsgd_pack": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "omf_qsgd_decode_packed": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p]),
@@ -92,7 +94,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 112  # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 113 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

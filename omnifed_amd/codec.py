@@ -438,6 +438,42 @@ class Plan:
                                     1 if accumulate else 0, ctypes.c_void_p(st)), "omf_qsgd_decode")
         return y_out
 
+    def qsgd_decode_sum(self, qs: Sequence[torch.Tensor], width: int, levels: int, norms: Sequence[torch.Tensor],
+                        y_out: Optional[torch.Tensor] = None, init: bool = False, divisor: Optional[float] = None,
+                        stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_sum: ``y = (init ? y : 0) + Σ_k decode(qs[k], norms[k])`` in list order, then
+        ``/ divisor`` — one pass over the arena instead of one accumulating decode per client (same
+        bytes).  ``init=False`` writes the whole arena, padding included (``0 / divisor``);
+        ``init=True`` extends ``y_out`` and leaves its padding alone.  ``divisor`` None: no division."""
+        width, levels = int(width), int(levels)
+        if width not in (8, 32):
+            raise ValueError(f"unsupported width={width}")
+        if levels <= 0:
+            raise ValueError(f"invalid level={levels}")
+        qs, norms = list(qs), list(norms)
+        if not qs or len(qs) != len(norms):
+            raise ValueError(f"qsgd_decode_sum needs one norm tensor per payload and at least one ({len(qs)}, {len(norms)})")
+        dev = self.device
+        qdt = torch.int8 if width == 8 else torch.int32
+        for k, (q, nm) in enumerate(zip(qs, norms)):
+            _need(q, f"qs[{k}]", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+            _need(nm, f"norms[{k}]", torch.float32, dev, self.nt, 4)
+        if y_out is None:
+            if init:
+                raise ValueError("init=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        n = len(qs)
+        qp = (ctypes.c_void_p * n)(*[q.data_ptr() for q in qs])
+        npp = (ctypes.c_void_p * n)(*[nm.data_ptr() for nm in norms])
+        st = stream if stream is not None else _stream(dev)
+        check(lib().omf_qsgd_decode_sum(self._h, qp, npp, n, width, levels, _ptr(y_out), 1 if init else 0, d,
+                                        ctypes.c_void_p(st)), "omf_qsgd_decode_sum")
+        return y_out
+
     # ------------------------------------------------------------ bit-packed wire (opt-in)
     def packed_words(self, levels: int) -> int:
         """32-bit words of the packed arena: ceil(arena_end / 32) groups of 32 elements, b words

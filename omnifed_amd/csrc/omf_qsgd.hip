@@ -1781,6 +1781,148 @@ __global__ __launch_bounds__(kThreads) void items_f32_kernel(const Item* __restr
   }
 }
 
+// N clients' payloads decoded and summed in one pass (omf_qsgd_decode_sum), in qsgd_decode_arena's
+// shape: one workgroup per arena-aligned block of 1 Ki elements (one quad per thread; two for int8
+// measured the same), all N payload quads of a thread loaded at once (unconditional, clamped), the binfo entry and the N norms scalar loads in
+// flight with them, the sum in registers (client order, __fadd_rn), one non-temporal store per quad.
+//   s = init ? y : +0;  s = fl32(s + dec_quad(q_c, norm_c[t]))  c = 0..N-1;  y = divisor != 0 ? s / divisor : s
+// The client pointers are kernel arguments indexed at compile time (N is a template parameter: a
+// runtime index into a by-value array is copied to scratch).  Boundary blocks go element by element,
+// as the decoder's; with `fill` they also write the padding of [0, arena_end) (fl32(+0 / divisor), or
+// +0): the bytes of memset, N accumulating decodes and omf_div_f32 over the arena.
+constexpr int kSumMax = 8;  // clients per launch; omf_qsgd_decode_sum chains groups
+template <int N>
+struct SumArgs {
+  const void* q[N];
+  const float* norm[N];
+  float* y;
+  float levels;      // fl32(levels)
+  float inv_levels;  // as DecArgs
+  float divisor;     // 0: no division
+  float pad_div;     // the whole call's divisor: what the padding is divided by (fill)
+  int32_t init;      // the sum starts from y (else from +0: y is not read)
+  int32_t fill;      // padding elements of [0, arena_end) are written
+};
+
+constexpr int64_t kSumBlk = (int64_t)kThreads * 4;  // elements per workgroup
+static_assert(kDecBlk % kSumBlk == 0, "whole sum blocks per binfo table block");
+template <int WIDTH, bool POW2, int N>
+__global__ __launch_bounds__(kThreads) void qsgd_decode_sum_arena(SumArgs<N> a, const uint32_t* __restrict__ binfo,
+                                                                  const int64_t* __restrict__ begins,
+                                                                  const int64_t* __restrict__ sizes, int32_t nt,
+                                                                  int64_t qlast, int64_t arena_end) {
+  const int64_t base = (int64_t)blockIdx.x * kSumBlk;
+  const int64_t e = base + 4 * (int64_t)threadIdx.x;
+  const int64_t ec = min(e, qlast);  // unconditional (clamped) loads, every client's
+  int32_t raw[N][WIDTH == 1 ? 1 : 4];
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    if (WIDTH == 1) {
+      raw[c][0] = *reinterpret_cast<const int32_t*>(reinterpret_cast<const int8_t*>(a.q[c]) + ec);
+    } else {
+      const i32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(reinterpret_cast<const int32_t*>(a.q[c]) + ec));
+      raw[c][0] = t[0]; raw[c][1] = t[1]; raw[c][2] = t[2]; raw[c][3] = t[3];
+    }
+  }
+  f32x4_t pv = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (a.init) pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(a.y + ec));
+  const uint32_t info = binfo[base / kDecBlk];
+  const int32_t t0 = (int32_t)(info & 0x7fffffffu);
+  DecArgs d{};  // dec_quad reads the levels only
+  d.levels = a.levels; d.inv_levels = a.inv_levels;
+  if (info >> 31) {  // the whole table block lies inside tensor t0
+    float norm[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) norm[c] = a.norm[c][t0];
+    float s[4] = {pv[0], pv[1], pv[2], pv[3]};
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      float yv[4];
+      dec_quad<WIDTH, false, POW2>(d, raw[c], norm[c], yv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = __fadd_rn(s[j], yv[j]);
+    }
+    if (a.divisor != 0.0f) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = s[j] / a.divisor;
+    }
+    store_nt(a.y + e, make_float4(s[0], s[1], s[2], s[3]));
+    return;
+  }
+  // boundary block: the quad's tensor, element by element
+  if (e >= arena_end) return;
+  const float pad = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
+  int32_t t = t0;
+  while (t + 1 < nt && e >= begins[t + 1]) ++t;
+  const int64_t tb = begins[t], te = tb + sizes[t];
+  if (e < tb || e >= te) {  // a quad of padding (offsets are multiples of 4: no tensor starts inside it)
+    if (a.fill)
+      for (int j = 0; j < 4; ++j)
+        if (e + j < arena_end) a.y[e + j] = pad;
+    return;
+  }
+  const bool part = e + 4 > te;  // the tensor's partial last quad: its bytes only (the payload may end here)
+  float s[4];
+  for (int j = 0; j < 4; ++j) s[j] = (a.init && e + j < te) ? a.y[e + j] : 0.0f;
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    int32_t rr[4] = {raw[c][0], WIDTH == 1 ? 0 : raw[c][1], WIDTH == 1 ? 0 : raw[c][2], WIDTH == 1 ? 0 : raw[c][3]};
+    if (part) {
+      if (WIDTH == 1) {
+        const int8_t* q8 = reinterpret_cast<const int8_t*>(a.q[c]);
+        uint32_t w = 0;
+        for (int j = 0; j < 3; ++j)
+          if (e + j < te) w |= (uint32_t)(uint8_t)q8[e + j] << (8 * j);
+        rr[0] = (int32_t)w;
+      } else {
+        const int32_t* q32 = reinterpret_cast<const int32_t*>(a.q[c]);
+        for (int j = 0; j < 3; ++j) rr[j] = e + j < te ? q32[e + j] : 0;
+        rr[3] = 0;
+      }
+    }
+    float yv[4];
+    dec_quad<WIDTH, false, POW2>(d, rr, a.norm[c][t], yv);
+    for (int j = 0; j < 4; ++j) s[j] = __fadd_rn(s[j], yv[j]);
+  }
+  for (int j = 0; j < 4; ++j) {
+    if (e + j < te) a.y[e + j] = a.divisor != 0.0f ? s[j] / a.divisor : s[j];
+    else if (a.fill && e + j < arena_end) a.y[e + j] = pad;
+  }
+}
+
+// The same for an arena of fewer than 4 elements (no whole quad to load): one thread per element,
+// byte / dword loads, `n` clients behind a uniform guard (compile-time indices all the same).
+template <int WIDTH, bool POW2>
+__global__ __launch_bounds__(64) void qsgd_decode_sum_tiny(SumArgs<kSumMax> a, int32_t n,
+                                                           const int64_t* __restrict__ begins,
+                                                           const int64_t* __restrict__ sizes, int32_t nt,
+                                                           int64_t arena_end) {
+  const int64_t i = threadIdx.x;
+  if (i >= arena_end) return;
+  int32_t t = -1;
+  for (int32_t u = 0; u < nt; ++u)
+    if (i >= begins[u] && i < begins[u] + sizes[u]) t = u;
+  if (t < 0) {
+    if (a.fill) a.y[i] = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
+    return;
+  }
+  DecArgs d{};
+  d.levels = a.levels; d.inv_levels = a.inv_levels;
+  float s = a.init ? a.y[i] : 0.0f;
+#pragma unroll
+  for (int c = 0; c < kSumMax; ++c) {
+    if (c < n) {
+      int32_t rr[4] = {0, 0, 0, 0};
+      rr[0] = WIDTH == 1 ? (int32_t)(uint8_t) reinterpret_cast<const int8_t*>(a.q[c])[i]
+                         : reinterpret_cast<const int32_t*>(a.q[c])[i];
+      float yv[4];
+      dec_quad<WIDTH, false, POW2>(d, rr, a.norm[c][t], yv);
+      s = __fadd_rn(s, yv[0]);
+    }
+  }
+  a.y[i] = a.divisor != 0.0f ? s / a.divisor : s;
+}
+
 }  // namespace
 
 // ====================================================================== host side
@@ -2677,3 +2819,106 @@ int omf_div_f32(float* y, int64_t n, float divisor, void* stream) {
 }
 
 }  // extern "C"
+
+// ---- omf_qsgd_decode_sum: one group of at most kSumMax clients per launch
+namespace {
+
+struct SumCall {
+  const omf_plan* p;
+  const void* const* q;
+  const float* const* norm;
+  float* y;
+  float levels, inv_levels, divisor, pad_div;
+  int32_t init, fill;
+  hipStream_t st;
+};
+
+template <int N>
+SumArgs<N> sum_args(const SumCall& c, int n) {
+  SumArgs<N> a{};
+  for (int k = 0; k < n; ++k) { a.q[k] = c.q[k]; a.norm[k] = c.norm[k]; }
+  a.y = c.y; a.levels = c.levels; a.inv_levels = c.inv_levels; a.divisor = c.divisor; a.pad_div = c.pad_div;
+  a.init = c.init; a.fill = c.fill;
+  return a;
+}
+
+template <int W, bool P, int N>
+void launch_sum_n(const SumCall& c) {
+  const omf_plan* p = c.p;
+  const int64_t qlast = (p->arena_end & ~(int64_t)3) - 4;  // the last whole quad (as decode_blocks)
+  const int64_t per = kDecBlk / kSumBlk;                   // sum blocks per table block
+  hipLaunchKernelGGL((qsgd_decode_sum_arena<W, P, N>), dim3((unsigned)(p->n_dec_blocks * per)), dim3(kThreads), 0,
+                     c.st, sum_args<N>(c, N), (const uint32_t*)p->d_dec_binfo, (const int64_t*)p->d_begins,
+                     (const int64_t*)p->d_sizes, p->nt, qlast, p->arena_end);
+}
+
+template <int W, bool P>
+void launch_sum(const SumCall& c, int n) {
+  if (c.p->arena_end < 4) {  // no whole quad: the element kernel
+    hipLaunchKernelGGL((qsgd_decode_sum_tiny<W, P>), dim3(1), dim3(64), 0, c.st, sum_args<kSumMax>(c, n), n,
+                       (const int64_t*)c.p->d_begins, (const int64_t*)c.p->d_sizes, c.p->nt, c.p->arena_end);
+    return;
+  }
+  static_assert(kSumMax == 8, "one case per group size");
+  switch (n) {
+    case 1: launch_sum_n<W, P, 1>(c); break;
+    case 2: launch_sum_n<W, P, 2>(c); break;
+    case 3: launch_sum_n<W, P, 3>(c); break;
+    case 4: launch_sum_n<W, P, 4>(c); break;
+    case 5: launch_sum_n<W, P, 5>(c); break;
+    case 6: launch_sum_n<W, P, 6>(c); break;
+    case 7: launch_sum_n<W, P, 7>(c); break;
+    default: launch_sum_n<W, P, 8>(c); break;
+  }
+}
+
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+}  // namespace
+
+extern "C" int omf_qsgd_decode_sum(omf_plan* p, const void* const* q, const float* const* norm, int32_t nclients,
+                                   int32_t width, int32_t levels, float* y, int32_t init, float divisor,
+                                   void* stream) {
+  if (!p) return fail(OMF_EINVAL, "plan is NULL");
+  if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
+  if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
+  if (nclients < 1) return fail(OMF_EINVAL, "omf_qsgd_decode_sum: nclients must be >= 1");
+  if (!q || !norm || !y) return fail(OMF_EINVAL, "q, norm and y_out must be non-NULL");
+  if (!aligned(y, 16)) return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
+  const size_t ybytes = (size_t)p->arena_end * 4;
+  const size_t qbytes = width == 8 ? (size_t)((p->arena_end + 3) & ~(int64_t)3) : (size_t)p->arena_end * 4;
+  for (int32_t k = 0; k < nclients; ++k) {
+    if (!q[k] || !norm[k]) return fail(OMF_EINVAL, "omf_qsgd_decode_sum: a NULL entry in q or norm");
+    if (!aligned(q[k], width == 8 ? 4 : 16))
+      return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
+    if (overlaps(y, ybytes, q[k], qbytes) || overlaps(y, ybytes, norm[k], (size_t)p->nt * 4))
+      return fail(OMF_EINVAL, "omf_qsgd_decode_sum: y_out overlaps a payload or norm buffer");
+  }
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
+  const bool pow2 = (levels & (levels - 1)) == 0;
+  SumCall c;
+  c.p = p; c.y = y; c.st = (hipStream_t)stream;
+  c.levels = (float)levels;
+  c.inv_levels = pow2 ? 1.0f / (float)levels : 0.0f;  // exact for a power of two
+  // Groups of at most kSumMax clients, chained: later groups start from y, the first fills the
+  // padding, the last divides.
+  for (int32_t k0 = 0; k0 < nclients; k0 += kSumMax) {
+    const int n = std::min<int32_t>(kSumMax, nclients - k0);
+    c.q = q + k0; c.norm = norm + k0;
+    c.init = (k0 > 0 || init) ? 1 : 0;
+    c.fill = (k0 == 0 && !init) ? 1 : 0;
+    c.divisor = k0 + n == nclients ? divisor : 0.0f;
+    c.pad_div = divisor;
+    if (width == 8) {
+      if (pow2) launch_sum<1, true>(c, n); else launch_sum<1, false>(c, n);
+    } else {
+      if (pow2) launch_sum<4, true>(c, n); else launch_sum<4, false>(c, n);
+    }
+    OMF_HIP(hipGetLastError());
+  }
+  return OMF_OK;
+}

@@ -15,8 +15,8 @@ weighted sum Σ_i decode(Q(w_i·x_i)) / Σ_i w_i is the path's only exchange ste
 * ``weighted_sum_reduce``: each rank decodes its own payload, then one RCCL
   ``reduce(SUM)`` of the fp32 arena to the root, which divides by Σw;
 * ``weighted_sum_gather``: RCCL ``gather`` of the int8/int32 payloads + norms to
-  the root (w/4 of the fp32 bytes over xGMI), which decode-accumulates them in
-  rank order (deterministic) and divides.
+  the root (w/4 of the fp32 bytes over xGMI), which sums their decodes in rank order
+  (deterministic) and divides: ``sum_payloads``, one ``omf_qsgd_decode_sum`` call.
 Top-K across GPUs (``topk_sparse_aggregate``): the reference's sparse aggregate
 (torch_mpi.py:302-359 → core.layerwise_decompress, core.py:62-71): every rank's
 (values, indices) all-gathered (or gathered to one root), scatter-added in rank order
@@ -83,6 +83,10 @@ class GpuOps:
     def div_(self, y, d):
         return codec.div_(y, d)
 
+    def decode_sum(self, qs, width, levels, norms, y, init, divisor):
+        """Σ_k decode(qs[k], norms[k]) in list order (from ``y`` when ``init``), ``/ divisor``: one pass."""
+        return self.plan.qsgd_decode_sum(qs, width, levels, norms, y_out=y, init=init, divisor=divisor)
+
     def topk_encode(self, x, ratio, residual, residual_mode, alpha, values=None, indices=None, tie_order="torch"):
         """The client's Top-K encode (the reference's selection where magnitudes tie: tie_order)."""
         values, indices, _ = self.plan.topk_encode(x, ratio, residual=residual, residual_mode=residual_mode,
@@ -135,7 +139,8 @@ class DeviceAggregator:
         return self.avg[o:o + n]
 
     def accumulate_layers(self, layers, number_samples: int = 0):
-        """Decode one client's update into the accumulator (global_grpc_server.py:108-111, 147-153).
+        """Decode one client's update into the accumulator (global_grpc_server.py:108-111, 147-153):
+        ``_stage_update`` then ``_apply_staged``.
 
         Every layer is checked and staged before the accumulator is touched (the reference decodes
         the whole update, then accumulates: a bad layer leaves acc as it was).  All QSGD layers go
@@ -145,10 +150,16 @@ class DeviceAggregator:
         Top-K layer are distinct, as every encoder's selection (torch.topk's, the reference's) is; a
         layer with more values than elements (which must repeat indices) is decoded alone with
         numpy's last-wins rule and added."""
+        self._check_fresh()
+        self._apply_staged(self._stage_update(layers), number_samples)
+
+    def _stage_update(self, layers):
+        """Validate one update and stage its payloads in the device; the accumulator is not touched.
+        Returns ``(q_args, t_args, adds)``: the QSGD arena ``(payload, width, level, norms)`` or None,
+        the Top-K selection ``(counts, values, indices)`` or None, and ``(name, tensor)`` dense terms."""
         from .hybrid.communicator.global_grpc_compression import (_decode_topk_layer, _validate_layer,
                                                                   check_topk_indices, stage_topk)
 
-        self._check_fresh()
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
         for L in layers:
@@ -220,6 +231,11 @@ class DeviceAggregator:
             if arr.numel() != n:
                 raise ValueError(f"Dense layer {L.layer_name!r}: {arr.numel()} values, expected {n}")
             dense_args.append((L.layer_name, arr.to(self.device, non_blocking=False)))
+        return q_args, t_args, dense_args + odd_args
+
+    def _apply_staged(self, staged, number_samples: int = 0):
+        """Add one staged update to the accumulator and advance the counters."""
+        q_args, t_args, adds = staged
         # --- accumulate (client terms in the reference's per-name order: one term per name)
         if q_args is not None:
             # Tensors absent from this update keep acc += (0 * q)/L = +0 (whatever q holds there:
@@ -228,10 +244,51 @@ class DeviceAggregator:
             self.plan.qsgd_decode(qd, width, level, nd, y_out=self.acc, accumulate=True)
         if t_args is not None:
             self.plan.topk_decode_counts(*t_args, y=self.acc, mode=2)
-        for name, arr in dense_args + odd_args:
+        for name, arr in adds:
             self._slice(name).add_(arr.reshape(-1))
         self.update_count += 1
         self.total_samples += int(number_samples)
+
+    def accumulate_many(self, updates, max_batch: int = 8):
+        """``accumulate_layers`` for a sequence of ``(layers, number_samples)`` in arrival order, with the
+        accumulator read and written once per run of QSGD-only updates instead of once per update.
+
+        Updates are staged in order.  Consecutive updates that hold only QSGD layers of one
+        ``(width, level)`` form a run of at most ``max_batch``, applied by ONE
+        ``qsgd_decode_sum(init=True)`` over their staged payload arenas (omf_qsgd_decode_sum: faster than
+        the per-update decode at every run length measured).  An update that also holds Top-K
+        or dense layers ends the run and is applied as ``accumulate_layers`` applies it.  If staging
+        update j raises, the updates before it are applied and counted, then the exception propagates:
+        the accumulator holds exactly what j - 1 ``accumulate_layers`` calls would have left.  Same
+        bytes and counters as one ``accumulate_layers`` call per update."""
+        self._check_fresh()
+        max_batch = max(int(max_batch), 1)
+        run: List[tuple] = []  # [(q_args, number_samples)] of one (width, level)
+
+        def flush():
+            batch = list(run)
+            run.clear()
+            if not batch:
+                return
+            _, width, level, _ = batch[0][0]
+            self.plan.qsgd_decode_sum([b[0][0] for b in batch], width, level, [b[0][3] for b in batch],
+                                      y_out=self.acc, init=True)
+            self.update_count += len(batch)
+            self.total_samples += sum(int(ns) for _, ns in batch)
+
+        try:
+            for layers, number_samples in updates:
+                staged = self._stage_update(layers)
+                q_args, t_args, adds = staged
+                if q_args is not None and t_args is None and not adds:
+                    if run and (run[0][0][1:3] != q_args[1:3] or len(run) >= max_batch):
+                        flush()
+                    run.append((q_args, number_samples))
+                else:
+                    flush()
+                    self._apply_staged(staged, number_samples)
+        finally:
+            flush()  # on a staging error too: everything before the bad update is applied
 
     def accumulate_updates(self, updates: Dict[str, torch.Tensor], compressor, number_samples: int = 0,
                            weight=None):
@@ -423,10 +480,32 @@ def weighted_sum_reduce(y: torch.Tensor, total_weight: float, ops, group=None, d
     return y
 
 
+def sum_payloads(bufs: Sequence[Tuple[torch.Tensor, torch.Tensor]], width: int, levels: int, acc: torch.Tensor,
+                 total_weight: float, ops) -> torch.Tensor:
+    """The root's aggregate of gathered ``(payload, norms)`` pairs: ``acc = Σ_k decode(bufs[k]) / total_weight``
+    with the clients added in list order, every byte of ``acc`` written (padding: ``0 / total_weight``).
+
+    An ``ops`` with ``decode_sum`` (``GpuOps``) makes ONE call that reads each payload once and writes
+    ``acc`` once (omf_qsgd_decode_sum); any other ``ops`` — the CPU oracle ops of the gloo tests — zeroes
+    ``acc``, decode-accumulates client by client and divides.  Same bytes either way.  The one call
+    covers exactly the plan's arena and a non-zero divisor; anything else takes the loop too."""
+    fused = getattr(ops, "decode_sum", None)
+    plan = getattr(ops, "plan", None)
+    if (fused is not None and bufs and float(total_weight) != 0.0
+            and (plan is None or acc.numel() == plan.arena_end)):
+        return fused([b[0] for b in bufs], width, levels, [b[1] for b in bufs], acc, False, float(total_weight))
+    acc.zero_()
+    for qb, nb in bufs:
+        ops.decode(qb, width, levels, nb, acc, True)
+    ops.div_(acc, float(total_weight))
+    return acc
+
+
 def weighted_sum_gather(q: torch.Tensor, norms: torch.Tensor, width: int, levels: int, acc: torch.Tensor,
                         total_weight: float, ops, group=None, dst: int = 0,
                         bufs: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None) -> torch.Tensor:
-    """Gather every rank's payload (+ norms) to ``dst``; it decode-accumulates them in rank order and divides."""
+    """Gather every rank's payload (+ norms) to ``dst``; it sums their decodes in rank order and divides
+    (``sum_payloads``)."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if rank == dst:
@@ -434,10 +513,7 @@ def weighted_sum_gather(q: torch.Tensor, norms: torch.Tensor, width: int, levels
             bufs = [(torch.empty_like(q), torch.empty_like(norms)) for _ in range(world)]
         dist.gather(q, gather_list=[b[0] for b in bufs], dst=dst, group=group)
         dist.gather(norms, gather_list=[b[1] for b in bufs], dst=dst, group=group)
-        acc.zero_()
-        for qb, nb in bufs:
-            ops.decode(qb, width, levels, nb, acc, True)
-        ops.div_(acc, float(total_weight))
+        sum_payloads(bufs, width, levels, acc, total_weight, ops)
     else:
         dist.gather(q, dst=dst, group=group)
         dist.gather(norms, dst=dst, group=group)
