@@ -2,15 +2,19 @@
 //
 // Not part of the C ABI.  omf_qsgd.hip creates, uploads and destroys a plan and launches the QSGD
 // kernels from it; omf_qsgd_pack.hip and omf_topk.hip read its arena tables and keep their
-// per-plan device tables in it.  The host tables come from omf_plan_layout.h.
+// per-plan device tables in it.  The host tables come from omf_plan_layout.h; Top-K's host state
+// (its workspace layout, made at the plan's first Top-K use, and its latest encode tables) is
+// omf_topk_layout.h's.
 #pragma once
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "../../include/omf_codec.h"
 #include "omf_common.h"
 #include "omf_plan_layout.h"
+#include "omf_topk_layout.h"
 
 namespace omf {
 
@@ -126,6 +130,11 @@ struct omf_plan {
   };
   std::vector<TopkTable> topk_tables;
   omf::TopkKnobs topk_knobs;
+  // Top-K encode: the caller workspace's layout (omf_topk.hip encode_ws; the size query takes a
+  // const plan) and the tables of the latest (ratio, sample size)
+  mutable std::once_flag topk_ws_once;
+  mutable omf::topk_layout::EncodeWsLayout topk_ws;
+  omf::topk_layout::EncodeSetup topk_setup;
   // Launches that use the sync block / granules are ordered across streams: a launch on a
   // stream other than the previous one first waits for the previous launch's event.
   hipEvent_t last_ev = nullptr;

@@ -34,6 +34,13 @@
 // descending sort of (|t'|bits << 32 | ~index) per tensor).
 // Decode is a scatter (mode 0 zero-fill, 1 overlay, 2 scatter-add); the arena zero-fill decode
 // with a workspace is tiled (topk_dec_place / topk_dec_tiles / topk_dec_overflow).
+//
+// The host side's integer code is omf_topk_layout.{h,cpp} (no HIP header, CPU-tested): the constants
+// shared with the kernels, the per-tensor rules (k, bucket slots, sampling stride, items, super-items:
+// one definition each, called from the kernels too), the encoder's constant tables (built on the host
+// and uploaded once per plan, ratio and sample size), the pipeline groups, the decoder's tables and
+// the carve of both workspaces.  This file keeps the kernels, the launches and what needs the HIP
+// runtime or rocPRIM (the sort's temporary, the CU count).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -55,25 +62,15 @@
 #include "../../include/omf_codec_experimental.h"
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_topk_layout.h"
 
 using namespace omf;
+using namespace omf::topk_layout;  // the constants and per-tensor rules shared with the host side
 
 namespace {
 
-constexpr int kBins = 1024;
 constexpr int kShift = 21;  // key (31 bits) >> 21 -> 10-bit bin (exact path)
-constexpr int kSBits = 13;  // sample histogram: exponent + 5 mantissa bits
-constexpr int kSBins = 1 << kSBits;
 constexpr int kSShift = 31 - kSBits;
-#ifndef OMF_SRUN  // experiment builds may override it (scripts/exp/tk_srun_ab.sh)
-#define OMF_SRUN 16
-#endif
-constexpr int kSRun = OMF_SRUN;  // a sample is a 64-byte run of 16 consecutive elements,
-constexpr int kSStride = 256;   // one run per >= 256 elements,
-// default: at most 2 Ki runs (32 Ki samples) per tensor (OMF_TOPK_SAMPLE_RUNS).  Llama-400M encode:
-// 1.024 ms at 2 Ki runs, 1.097 at 4 Ki, 1.142 at 8 Ki, 1.194 at 16 Ki (scripts/exp/tk_runs_sweep.py):
-// the sample's random sectors cost more than the tighter threshold saves in the bucket kernels.
-constexpr int kSMaxRuns = 2048;
 // The threshold bin's margin over the expected k*S/n samples: OMF_THR_Z sigma + OMF_THR_C (a
 // performance knob only — a tensor left with fewer than k candidates takes the exact redo).
 #ifndef OMF_THR_Z  // experiment builds may override them (scripts/exp/tk_thr_ab.sh)
@@ -83,45 +80,22 @@ constexpr int kSMaxRuns = 2048;
 #define OMF_THR_C 32.0
 #endif
 constexpr int kV = 16;
-constexpr int64_t kSub = (int64_t)kV * kThreads * 4;
+static_assert(kSub == (int64_t)kV * kThreads * 4, "a flat item: kV float4 per thread");
 // Composite candidate key: index << 39 | tensor << 31 | (2^31 - 1 - |t'|bits).  Candidates are
 // emitted in index order within each tensor, so a stable radix sort of the low 39 bits alone
 // gives (tensor ascending, |t'| descending, index ascending): 5 digit passes instead of 8.
 constexpr int kSortBits = 39;
-// Bucket sort of the candidates (the fast path): fine bins per tensor (<= kFineMax), buckets
-// of whole fine bins whose rank starts fall in one kBucketHalf-wide window (so <= 2x that
-// many keys when no fine bin exceeds kBucketHalf), each sorted in LDS by one block.
-constexpr int kCoarse = 1024;         // coarse (sample-resolution) bins mapped per tensor
-constexpr int kFineMax = 16384;       // fine bins per tensor
 constexpr int kFineMaxBits = 18;      // a coarse bin splits by at most the rest of the mantissa
 #ifndef OMF_FINE_MARGIN  // experiment builds may override it (scripts/exp/tk_margin_ab.sh)
 #define OMF_FINE_MARGIN 8
 #endif
 constexpr int kFineMargin = OMF_FINE_MARGIN;  // a fine bin expects <= kBucketHalf / 8 elements
-constexpr int kBucketHalf = 2048;
 constexpr int kBT = 512;              // bucket-sort block: 512 threads x 8 keys = 2 kBucketHalf
 constexpr int kBI = 8;
 constexpr int kPlanMaxBuckets = (1 << 25) / kBucketHalf + 2;  // topk_plan's rule (no big-bin buckets)
-// A tensor's bucket-key region: k + kBucketPad keys (the k-th key's bin may run past rank k by up to
-// one bucket's worth: a fine bin of up to 2 kBucketHalf keys sits in a bucket of its own).
-constexpr int kBucketPad = 2 * kBucketHalf;
 constexpr int kMaxBigBins = 128;  // kept fine bins over kBucketHalf keys per tensor on the fast path
-#ifndef OMF_TK_SUBPER  // experiment builds may override it
-#define OMF_TK_SUBPER 512
-#endif
-constexpr int kSubPer = OMF_TK_SUBPER;        // elements per block of the fused pass
 constexpr int kSubThreads = kSubPer / 4;      // one float4 per thread: 128 threads, two waves
 constexpr int kSubWaves = kSubThreads / 64;
-constexpr int kSubsPerItem = (int)(kSub / kSubPer);  // 32
-constexpr int kSupItems = 1024 / kSubsPerItem;  // items per super-item (x 32 sub-chunks = 1024 runs)
-
-// One bucket of the fast path: its keys at bkeys[key_off, + count), its first rank `start`
-// within the tensor; count | tensor << 16 (a bucket holds <= 2 kBucketHalf keys).
-struct BucketRec {
-  uint64_t key_off;
-  uint32_t start;
-  uint32_t count_tensor;
-};
 
 using Item = omf::plan_layout::Item;  // the plan's flat items (omf_plan_layout.h)
 
@@ -167,84 +141,12 @@ __device__ __forceinline__ float tprime(float x, float r, float alpha) {
   return MODE == 1 ? __fadd_rn(r, t) : t;
 }
 
-// Per tensor: k, the output offset, the tensor's flat-item range (items are 16 Ki
-// sub-chunks in tensor order: omf_qsgd.hip upload_plan), its bucket-table range (bbase) and
-// bucket-buffer region (kb2, k + kBucketPad keys).  One block; nt may exceed it.  Clears the
-// call's status words.
-// Bucket slots of a tensor: the kBucketHalf-wide rank windows below k, plus one bucket of its own for
-// each "big" fine bin (> kBucketHalf keys, topk_scatter_planned), at most k / (kBucketHalf + 1) + 1 of them.
-__host__ __device__ __forceinline__ uint32_t bucket_slots(int64_t k) { return (uint32_t)(2 * (k / kBucketHalf) + 3); }
-
-__global__ __launch_bounds__(kThreads) void topk_setup(const int64_t* __restrict__ tsize, int32_t nt, double ratio,
-                                                       int64_t* __restrict__ kk, int64_t* __restrict__ koff,
-                                                       uint32_t* __restrict__ tfirst, uint32_t* __restrict__ tlast,
-                                                       uint32_t* __restrict__ bbase, int64_t* __restrict__ kb2,
-                                                       uint32_t* __restrict__ sbase, uint32_t* __restrict__ status,
-                                                       uint32_t seq) {
-  __shared__ int64_t s_k[kThreads], s_i[kThreads], s_b[kThreads];
-  __shared__ uint32_t s_s[kThreads];
-  if (threadIdx.x < 4) status[threadIdx.x] = threadIdx.x == 3 ? seq : 0u;  // [3]: this call's sequence number
-  int64_t carry_k = 0, carry_i = 0, carry_b = 0;
-  uint32_t carry_s = 0;
-  for (int32_t t0 = 0; t0 < nt; t0 += kThreads) {
-    const int32_t t = t0 + (int32_t)threadIdx.x;
-    int64_t k = 0, ni = 0, nb = 0;
-    uint32_t ns = 0;
-    if (t < nt) {
-      k = (int64_t)((double)tsize[t] * ratio);
-      if (k < 1) k = 1;
-      ni = (tsize[t] + kSub - 1) / kSub;
-      nb = bucket_slots(k);
-      ns = (uint32_t)((ni + kSupItems - 1) / kSupItems);
-    }
-    s_k[threadIdx.x] = k;
-    s_i[threadIdx.x] = ni;
-    s_b[threadIdx.x] = nb;
-    s_s[threadIdx.x] = ns;
-    __syncthreads();
-    for (int o = 1; o < kThreads; o <<= 1) {  // inclusive scans
-      const int64_t ak = threadIdx.x >= (unsigned)o ? s_k[threadIdx.x - o] : 0;
-      const int64_t ai = threadIdx.x >= (unsigned)o ? s_i[threadIdx.x - o] : 0;
-      const int64_t ab = threadIdx.x >= (unsigned)o ? s_b[threadIdx.x - o] : 0;
-      const uint32_t as = threadIdx.x >= (unsigned)o ? s_s[threadIdx.x - o] : 0u;
-      __syncthreads();
-      s_k[threadIdx.x] += ak;
-      s_i[threadIdx.x] += ai;
-      s_b[threadIdx.x] += ab;
-      s_s[threadIdx.x] += as;
-      __syncthreads();
-    }
-    if (t < nt) {
-      kk[t] = k;
-      koff[t] = carry_k + s_k[threadIdx.x] - k;
-      tfirst[t] = (uint32_t)(carry_i + s_i[threadIdx.x] - ni);
-      tlast[t] = (uint32_t)(carry_i + s_i[threadIdx.x] - 1);
-      bbase[t] = (uint32_t)(carry_b + s_b[threadIdx.x] - nb);
-      sbase[t] = carry_s + s_s[threadIdx.x] - ns;
-      kb2[t] = carry_k + s_k[threadIdx.x] - k + (int64_t)t * kBucketPad;
-      if (t == nt - 1) {
-        koff[nt] = carry_k + s_k[threadIdx.x];
-        bbase[nt] = (uint32_t)(carry_b + s_b[threadIdx.x]);
-        sbase[nt] = carry_s + s_s[threadIdx.x];
-      }
-    }
-    carry_k += s_k[kThreads - 1];
-    carry_i += s_i[kThreads - 1];
-    carry_b += s_b[kThreads - 1];
-    carry_s += s_s[kThreads - 1];
-    __syncthreads();
-  }
-}
-
 // Passes 1+2 (one launch, topk_sample): R = ceil(n / stride) runs, stride = max(256,
 // ceil(n / max_runs)); run j covers 16 aligned elements at j*stride + 16 * (hash(.) % (span/16))
 // (a whole 64-byte sector: random sectors, not elements, are what the sample costs), so
 // S <= 16 R samples go into a histogram of the top 13 bits of |t'|; then the bin whose
 // suffix holds k*S/n + 6 sqrt(k*S/n) + 32 samples (0 = every element, for tensors too small
 // to sample).  Four lanes read one run (float4 each).
-__device__ __forceinline__ int64_t sample_stride(int64_t n, int64_t max_runs) {
-  return max((int64_t)kSStride, (n + max_runs - 1) / max_runs);
-}
 // Sampling is split over the tensor's runs: kSRunsPerBlock runs per block (a 16 Ki-run tensor
 // is 32 blocks on 32 CUs instead of one CU doing all its loads and contended LDS histogram
 // atomics), each block adding its LDS histogram's non-empty bins into the tensor's global
@@ -254,13 +156,6 @@ __device__ __forceinline__ int64_t sample_stride(int64_t n, int64_t max_runs) {
 // (sample_threshold_tensor), so no second launch and no tail of one-block-per-tensor work
 // after the last sample.  smap: per block, (tensor, first run).  Block 0 also clears this
 // call's status words.
-// 2 Ki runs per block = one block per tensor at the default sample size: its LDS histogram is the
-// tensor's, so it derives the threshold at once, with no global flush (Llama-400M: 54 -> 37 us
-// against 512 runs per block, scripts/exp/tk_sblock_ab.sh); larger samples still split.
-#ifndef OMF_SRUNS_PER_BLOCK  // experiment builds may override it
-#define OMF_SRUNS_PER_BLOCK 2048
-#endif
-constexpr int kSRunsPerBlock = OMF_SRUNS_PER_BLOCK;
 #ifndef OMF_SAMPLE_HIST_LATE  // experiment builds: 0 clears the redo histogram before the threshold's barriers
 #define OMF_SAMPLE_HIST_LATE 1
 #endif
@@ -418,7 +313,7 @@ __global__ __launch_bounds__(1024) void topk_sample(const float* __restrict__ x,
   for (int b = threadIdx.x; b < kSBins; b += 1024) h[b] = 0;
   if (threadIdx.x == 0) s_zero = 0;
   const int64_t base = tbegin[t], n = tsize[t];
-  const int64_t stride = sample_stride(n, max_runs), nr = (n + stride - 1) / stride;
+  const int64_t stride = sample_stride(n, max_runs), nr = sample_runs(n, stride);
   const int64_t r1 = min(r0 + (int64_t)kSRunsPerBlock, nr);
   const uint32_t salt = (uint32_t)t * 0x9E3779B9u;
   const int q = threadIdx.x & (kLanesPerRun - 1);  // float4 of the run
@@ -458,7 +353,7 @@ __global__ __launch_bounds__(1024) void topk_sample(const float* __restrict__ x,
   for (int o = 32; o > 0; o >>= 1) zc += __shfl_xor(zc, o, 64);
   if ((threadIdx.x & 63) == 0 && zc) atomicAdd(&s_zero, zc);
   __syncthreads();
-  const uint32_t nblk = (uint32_t)((nr + kSRunsPerBlock - 1) / kSRunsPerBlock);
+  const uint32_t nblk = sample_blocks(nr);
   if (nblk == 1) {  // the tensor's whole sample is in this block's histogram (the usual case)
 #ifdef OMF_EXP_SAMPLE_TS
     const uint64_t ts2 = wall_clock64();
@@ -1203,7 +1098,6 @@ __device__ void topk_plan_tensor(int t, const int64_t* __restrict__ kk, const ui
 // SMALL (every tensor of the launch has <= kScatterSmallB bucket slots): the tensor's bucket
 // table is staged in LDS as 16-bit entries, so the per-key bucket lookup is an LDS read instead
 // of a global load that waits on the key load (two such round trips per key otherwise).
-constexpr uint32_t kScatterSmallB = 4096;
 #ifndef OMF_SCATTER_CACHE  // key loads per thread (x4) kept in registers between the two phases
 #define OMF_SCATTER_CACHE 3
 #endif
@@ -1753,7 +1647,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 // with a block scan; value = t' (the sign of the zero), residual := t' - t' (+0).  Run by the exact
 // tail's workgroups when the verdict reports a zero fill and no fallback (round 6; rounds 4-5 ran
 // it as a launch of its own, queued by the host after it had read the verdict).
-constexpr int kZChunk = 2 * kSubPer;  // elements per zero-fill chunk (kThreads x 4)
 static_assert(kZChunk == 4 * kThreads, "one float4 of a zero-fill chunk per thread");
 __device__ void zero_fill_chunk(uint2 zm, const uint32_t* __restrict__ zcnt, const int64_t* __restrict__ kk,
                                 const int64_t* __restrict__ koff, const int64_t* __restrict__ tbegin,
@@ -1876,7 +1769,6 @@ __device__ __forceinline__ int koff_tensor(const int64_t* koff, int nt, int64_t 
 //              ascending, the order the bucket sort gives
 //   gather     values / int64 indices of each tensor's first k keys, residual t' - t' there.
 // Sizes come from the device (the candidate count), so nothing is read back to the host.
-constexpr int kRadixDigits = 256;
 constexpr int kRadixPasses = (kSortBits + 7) / 8;  // 5
 constexpr uint32_t kTailWaitTicks = 20000000u;      // 200 ms of the 100 MHz wall clock: a guard only
 
@@ -2219,7 +2111,6 @@ __global__ __launch_bounds__(kThreads) void topk_scatter(const float* __restrict
 // koff[t] = sum_{u<t} k_u, tensor-local indices): y[begin_t + idx] = v (mode 0/1) or += v (2).
 // Indices are unique within a client, so the read-modify-write needs no atomics.  koff comes from
 // the plan's decode table (a ratio's k_t, or a received message's counts; k_t may be 0).
-constexpr int kArenaMaxTensors = 4096;
 
 __global__ __launch_bounds__(kThreads) void topk_scatter_arena(const float* __restrict__ values,
                                                                const int64_t* __restrict__ indices,
@@ -2299,14 +2190,11 @@ __global__ __launch_bounds__(kThreads) void topk_dup_bits(const int64_t* __restr
 // goes to an overflow list), then one workgroup per super-tile stages its bucket in LDS, builds
 // each 16 Ki-element sub-tile in LDS (zeros + its values) and streams it out with 16-byte
 // non-temporal stores; a last kernel applies the (normally empty) overflow list.
-constexpr int kDecSuperBits = 16;
 #ifndef OMF_DEC_SUB_BITS  // experiment builds may override it (scripts/exp/tk_dec_ab.sh)
 #define OMF_DEC_SUB_BITS 14
 #endif
 constexpr int kDecSubBits = OMF_DEC_SUB_BITS;
 constexpr int kDecSubs = 1 << (kDecSuperBits - kDecSubBits);
-constexpr int kDecMaxSuper = 16384;  // LDS bins of a place block (arenas <= 2^30 elements)
-constexpr int kDecChunk = 4096;      // selected values per place block
 #ifndef OMF_DEC_TILE_THREADS  // experiment builds may override it (scripts/exp/tk_dec_ab.sh)
 #define OMF_DEC_TILE_THREADS 512
 #endif
@@ -2528,8 +2416,6 @@ __global__ __launch_bounds__(kThreads) void topk_dec_overflow(uint32_t* __restri
 
 namespace {
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // Per host thread and device: the group pipeline's second stream and its events (made on first
 // use; experiment builds only use more than one group).
 struct HostSync {
@@ -2570,18 +2456,11 @@ int pipe_streams(HostSync* h) {
   return OMF_OK;
 }
 
-// Pipeline groups of the sampled path: contiguous tensor ranges of about equal element counts.
-// Each group's chain (sample -> fused pass -> fine histogram -> plan -> bucket scatter -> bucket
-// sort) is one run of launches on one of two streams, alternating, so that one group's
-// latency-bound kernels (the last sample blocks, the per-tensor plans, the bucket sorts) run
-// beside the next group's streaming pass instead of after the whole arena's.
-struct Group {
-  int32_t t0 = 0, t1 = 0;                           // tensors [t0, t1)
-  uint32_t sb0 = 0, nsb = 0, sub0 = 0, nsub = 0;    // sample blocks, fused-pass blocks
-  uint32_t sup0 = 0, nsup = 0, bk0 = 0, nbk = 0;    // super-items, bucket slots
-  uint32_t nb_max = 0;                              // most bucket slots of one tensor
-};
-
+// Pipeline groups of the sampled path (topk_layout::make_groups): each group's chain (sample -> fused
+// pass -> fine histogram -> plan -> bucket scatter -> bucket sort) is one run of launches on one of two
+// streams, alternating, so that one group's latency-bound kernels (the last sample blocks, the
+// per-tensor plans, the bucket sorts) run beside the next group's streaming pass instead of after the
+// whole arena's.
 int topk_group_count(const omf_plan* p, const TopkKnobs& kn) {
   // Off by default: measured on Llama-400M (scripts/exp/tk_env_ab.py) more groups only add time —
   // 1.089 ms with one group, 1.156 / 1.192 / 1.266 ms with 2 / 3 / 4 (the latency-bound kernels
@@ -2589,46 +2468,6 @@ int topk_group_count(const omf_plan* p, const TopkKnobs& kn) {
   int g = kn.groups;
   if (p->arena_end < ((int64_t)1 << 24)) g = 1;  // small arenas: launch-bound
   return std::max(1, std::min(g, std::min(16, p->nt)));
-}
-
-std::vector<Group> make_groups(const std::vector<int64_t>& sizes, double ratio, int64_t max_runs, int G) {
-  const int32_t nt = (int32_t)sizes.size();
-  int64_t total = 0;
-  for (int64_t n : sizes) total += n;
-  std::vector<Group> gs;
-  Group cur;
-  uint32_t sb = 0, sub = 0, sup = 0, bk = 0;
-  int64_t cum = 0;
-  for (int32_t t = 0; t < nt; ++t) {
-    const int64_t n = sizes[t];
-    const int64_t stride = std::max<int64_t>(kSStride, (n + max_runs - 1) / max_runs);  // as setup_table
-    const uint32_t nsb = (uint32_t)(((n + stride - 1) / stride + kSRunsPerBlock - 1) / kSRunsPerBlock);
-    const int64_t ni = (n + kSub - 1) / kSub;  // as topk_setup
-    const uint32_t ns = (uint32_t)((ni + kSupItems - 1) / kSupItems);
-    const uint32_t nb = (uint32_t)bucket_slots(omf_topk_k(n, ratio));
-    cur.nsb += nsb;
-    cur.nsub += (uint32_t)(ni * kSubsPerItem);
-    cur.nsup += ns;
-    cur.nbk += nb;
-    cur.nb_max = std::max(cur.nb_max, nb);
-    sb += nsb;
-    sub += (uint32_t)(ni * kSubsPerItem);
-    sup += ns;
-    bk += nb;
-    cum += n;
-    const int g = (int)gs.size();
-    if (t == nt - 1 || (g < G - 1 && cum * G >= total * (int64_t)(g + 1))) {
-      cur.t1 = t + 1;
-      gs.push_back(cur);
-      cur = Group{};
-      cur.t0 = t + 1;
-      cur.sb0 = sb;
-      cur.sub0 = sub;
-      cur.sup0 = sup;
-      cur.bk0 = bk;
-    }
-  }
-  return gs;
 }
 
 // The plan's Top-K settings: in experiment builds (omf::knob) the OMF_TOPK_* environment read once, at
@@ -2678,113 +2517,21 @@ bool global_path(const omf_plan* p) {
 size_t sort_tmp_bytes(const omf_plan* p) {
   const int64_t size = p->arena_end;
   const int32_t nt = p->nt;
+  if (global_path(p)) return 4 * (size_t)kRadixDigits * tail_grid(p->device);  // the exact tail's digit table
   size_t bytes = 0;
   uint64_t* dummy = nullptr;
-  if (global_path(p)) {
-    (void)dummy;
-    bytes = 4 * (size_t)kRadixDigits * tail_grid(p->device);  // the exact tail's digit table
-  } else {
-    uint32_t* off = nullptr;
-    (void)rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, dummy, dummy, (unsigned int)size, (unsigned int)nt,
-                                                  off, off, 0, 64, (hipStream_t)0, false);
-  }
+  uint32_t* off = nullptr;
+  (void)rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, dummy, dummy, (unsigned int)size, (unsigned int)nt,
+                                                off, off, 0, 64, (hipStream_t)0, false);
   return bytes;
 }
 
-// Workspace: everything up to `zero_end` is cleared once per call on the exact path; the
-// sampled path clears its redo histograms in topk_sample and writes the rest.
-struct WsLayout {
-  size_t hist, bin, cnt, flag, status, zero_end, tkey, zcnt, koff, kk, tfirst, tlast, seg_b, seg_e, cstart,
-      sub_cnt, item_cnt, item_off, cand, sorted, tmp, total, tmp_bytes, bbase, kb2, fmap, tlo, fcount, fhist,
-      fbucket, fse, bstart, brec, bfill, nb_max, sbase, thi;
-};
-
-// Bucket-table slots for any ratio (k <= n).
-size_t bucket_slots_max(const omf_plan* p) {
-  size_t nb = 0;
-  for (int64_t n : p->sizes) nb += (size_t)bucket_slots(n);
-  return nb;
+// The caller workspace's layout (topk_layout::encode_ws_layout), kept in the plan: made at the plan's
+// first Top-K use (sizing the library sort is not free, and every call needs it).
+const EncodeWsLayout& encode_ws(const omf_plan* p) {
+  std::call_once(p->topk_ws_once, [p] { p->topk_ws = encode_ws_layout(p->sizes, p->arena_end, sort_tmp_bytes(p)); });
+  return p->topk_ws;
 }
-
-WsLayout layout_uncached(const omf_plan* p);
-
-// The layout depends on the plan's shape only; the last one computed on this thread is kept
-// (sizing the library sort is not free, and this runs on every call).
-WsLayout layout(const omf_plan* p) {
-  struct Key {
-    const omf_plan* p;
-    int64_t ae;
-    int32_t nt;
-  };
-  thread_local Key key{nullptr, -1, -1};
-  thread_local WsLayout cached;
-  const Key k{p, p->arena_end, p->nt};
-  if (k.p != key.p || k.ae != key.ae || k.nt != key.nt) {
-    cached = layout_uncached(p);
-    key = k;
-  }
-  return cached;
-}
-
-WsLayout layout_uncached(const omf_plan* p) {
-  const int32_t nt = p->nt;
-  const int64_t ae = p->arena_end;
-  WsLayout L;
-  size_t o = 0;
-  L.hist = o; o = align256(o + 4 * (size_t)nt * kBins);
-  L.bin = o; o = align256(o + 4 * (size_t)nt);
-  L.cnt = o; o = align256(o + 4 * (size_t)nt);
-  L.flag = o; o = align256(o + 4 * (size_t)nt);
-  L.status = o; o = align256(o + 16);
-  L.zero_end = o;
-  L.tkey = o; o = align256(o + 4 * (size_t)nt);
-  L.zcnt = o; o = align256(o + 4 * (size_t)nt);
-  L.koff = o; o = align256(o + 8 * (size_t)(nt + 1));
-  L.kk = o; o = align256(o + 8 * (size_t)nt);
-  L.tfirst = o; o = align256(o + 4 * (size_t)nt);
-  L.tlast = o; o = align256(o + 4 * (size_t)nt);
-  L.seg_b = o; o = align256(o + 4 * (size_t)nt);
-  L.seg_e = o; o = align256(o + 4 * (size_t)nt);
-  L.cstart = o; o = align256(o + 8 * (size_t)nt);
-  const int64_t n_items = p->n_flat;
-  L.sub_cnt = o; o = align256(o + 4 * (size_t)n_items * kSubsPerItem);
-  L.item_cnt = o; o = align256(o + 4 * (size_t)n_items);
-  L.item_off = o; o = align256(o + 4 * (size_t)n_items);
-  L.cand = o; o = align256(o + 8 * (size_t)ae);
-  // the fallback's packed keys, or the fast path's buckets (k_t + kBucketPad per tensor)
-  L.sorted = o; o = align256(o + 8 * ((size_t)ae + (size_t)nt * kBucketPad));
-  L.bbase = o; o = align256(o + 4 * (size_t)(nt + 1));
-  L.sbase = o; o = align256(o + 4 * (size_t)(nt + 1));
-  L.kb2 = o; o = align256(o + 8 * (size_t)nt);
-  L.fmap = o; o = align256(o + 4 * (size_t)nt * kCoarse);
-  L.tlo = o; o = align256(o + 4 * (size_t)nt);
-  L.thi = o; o = align256(o + 4 * (size_t)nt);
-  L.fcount = o; o = align256(o + 4 * (size_t)nt);
-  L.fhist = o; o = align256(o + 4 * (size_t)nt * kFineMax);
-  L.fbucket = o; o = align256(o + 4 * (size_t)nt * kFineMax);
-  L.fse = o; o = align256(o + 4 * (size_t)nt * kFineMax);
-  L.nb_max = bucket_slots_max(p);
-  L.bstart = o; o = align256(o + 4 * L.nb_max);
-  L.brec = o; o = align256(o + sizeof(BucketRec) * L.nb_max);
-  L.bfill = o; o = align256(o + 4 * L.nb_max);
-  L.tmp_bytes = sort_tmp_bytes(p);
-  L.tmp = o; o = align256(o + L.tmp_bytes);
-  L.total = o;
-  return L;
-}
-
-// Per (plan, ratio, sample size) constant tables of the encoder, plan-owned
-// (topk_table, omf_plan.h), made once: topk_setup's per-tensor k / offsets / item ranges /
-// bucket and super-item bases, the sampling blocks' (tensor, first run) map, the sample
-// histograms gh (zeroed here once, left zeroed by every call) and the arrival counters of the
-// sample (per tensor) and plan kernels (likewise).
-struct SetupTable {
-  int64_t *kk, *koff, *kb2;
-  uint32_t *tfirst, *tlast, *bbase, *sbase, *smap, *gh, *gz, *done, *arrive;
-  uint32_t* supinfo;  // per super-item {tensor, first item, items, first super-item of its tensor}
-  uint32_t* zmap;     // per zero-fill chunk {tensor, 1 Ki-element chunk}: the chunks below index k_t
-  int32_t nsb, nzb;
-};
 
 // Runs sampled per tensor at most (a performance knob only: the selection is exact for any
 // sample; TopkKnobs::sample_runs overrides it for experiments).
@@ -2811,88 +2558,49 @@ unsigned long long* device_stats(omf_plan* p, hipStream_t st) {
   return static_cast<unsigned long long*>(d);
 }
 
-int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uint32_t* status, SetupTable* out) {
-  const std::vector<int64_t>& sizes = p->sizes;
-  const int32_t nt = (int32_t)sizes.size();
-  std::vector<uint32_t> smap;
-  for (int32_t t = 0; t < nt; ++t) {  // sampling blocks: as sample_stride on the device
-    const int64_t n = sizes[t];
-    const int64_t stride = std::max<int64_t>(kSStride, (n + max_runs - 1) / max_runs);
-    const int64_t nr = (n + stride - 1) / stride;
-    for (int64_t r0 = 0; r0 < nr; r0 += kSRunsPerBlock) {
-      smap.push_back((uint32_t)t);
-      smap.push_back((uint32_t)r0);
-    }
-  }
-  std::vector<uint32_t> supinfo;  // as topk_setup's super-item bases
-  uint32_t item0 = 0;
-  for (int32_t t = 0; t < nt; ++t) {
-    const uint32_t ni = (uint32_t)((sizes[t] + kSub - 1) / kSub);
-    for (uint32_t i = 0; i < ni; i += kSupItems) {
-      supinfo.push_back((uint32_t)t);
-      supinfo.push_back(item0 + i);
-      supinfo.push_back(std::min<uint32_t>(kSupItems, ni - i));
-      supinfo.push_back(i == 0 ? 1u : 0u);
-    }
-    item0 += ni;
-  }
-  std::vector<uint32_t> zmap;  // the zero fill's chunks (zero_fill_chunk)
-  for (int32_t t = 0; t < nt; ++t) {
-    const int64_t k = std::min(omf_topk_k(sizes[t], ratio), sizes[t]);
-    for (int64_t x = 0; x * kZChunk < k; ++x) {
-      zmap.push_back((uint32_t)t);
-      zmap.push_back((uint32_t)x);
-    }
-  }
-  size_t o = 0;
-  const size_t o_kk = o; o = align256(o + 8 * (size_t)nt);
-  const size_t o_koff = o; o = align256(o + 8 * ((size_t)nt + 1));
-  const size_t o_kb2 = o; o = align256(o + 8 * (size_t)nt);
-  const size_t o_tf = o; o = align256(o + 4 * (size_t)nt);
-  const size_t o_tl = o; o = align256(o + 4 * (size_t)nt);
-  const size_t o_bb = o; o = align256(o + 4 * ((size_t)nt + 1));
-  const size_t o_sb = o; o = align256(o + 4 * ((size_t)nt + 1));
-  const size_t o_sm = o; o = align256(o + 4 * smap.size());
-  const size_t o_si = o; o = align256(o + 4 * supinfo.size());
-  const size_t o_zm = o; o = align256(o + 4 * std::max<size_t>(zmap.size(), 2));
-  const size_t o_done = o; o = align256(o + 16);
-  const size_t o_arr = o; o = align256(o + 4 * (size_t)nt);
-  const size_t o_gz = o; o = align256(o + 4 * (size_t)nt);
-  const size_t o_gh = o; o = align256(o + 4 * (size_t)nt * kSBins);
+// The encoder's constant tables for (ratio, sample size): topk_layout::build_encode_tables' vectors in a
+// plan-owned device table (topk_table, omf_plan.h), uploaded once; the plan keeps the latest host and
+// device side (EncodeSetup).  The call that makes a table also clears the workspace's four verdict
+// words (the kernel that once computed these tables on the device wrote them too).
+int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uint32_t* status,
+                const EncodeSetup** out) {
+  EncodeSetup& es = p->topk_setup;
+  *out = &es;
+  uint64_t bits;
+  std::memcpy(&bits, &ratio, 8);
+  if (es.valid && es.ratio_bits == bits && es.max_runs == max_runs) return OMF_OK;
+  es.valid = false;
+  es.host = build_encode_tables(p->sizes, ratio, max_runs);
+  const EncodeTables& h = es.host;
+  const SetupCarve sc = setup_table_carve(h);
   bool fresh = false;
   uint64_t* host = nullptr;
-  uint64_t key;
-  std::memcpy(&key, &ratio, 8);
-  key ^= kSetupTag ^ ((uint64_t)max_runs * 0x9E3779B97F4A7C15ull);
-  uint8_t* d = static_cast<uint8_t*>(topk_table(p, key, o, &fresh, &host));
+  const uint64_t key = bits ^ kSetupTag ^ ((uint64_t)max_runs * 0x9E3779B97F4A7C15ull);
+  uint8_t* d = static_cast<uint8_t*>(topk_table(p, key, sc.carve.bytes(), &fresh, &host));
   if (!d) return fail(OMF_ENOMEM, "omf_topk_encode: table allocation failed");
-  out->kk = reinterpret_cast<int64_t*>(d + o_kk);
-  out->koff = reinterpret_cast<int64_t*>(d + o_koff);
-  out->kb2 = reinterpret_cast<int64_t*>(d + o_kb2);
-  out->tfirst = reinterpret_cast<uint32_t*>(d + o_tf);
-  out->tlast = reinterpret_cast<uint32_t*>(d + o_tl);
-  out->bbase = reinterpret_cast<uint32_t*>(d + o_bb);
-  out->sbase = reinterpret_cast<uint32_t*>(d + o_sb);
-  out->smap = reinterpret_cast<uint32_t*>(d + o_sm);
-  out->supinfo = reinterpret_cast<uint32_t*>(d + o_si);
-  out->done = reinterpret_cast<uint32_t*>(d + o_done);
-  out->arrive = reinterpret_cast<uint32_t*>(d + o_arr);
-  out->gh = reinterpret_cast<uint32_t*>(d + o_gh);
-  out->gz = reinterpret_cast<uint32_t*>(d + o_gz);
-  out->zmap = reinterpret_cast<uint32_t*>(d + o_zm);
-  out->nsb = (int32_t)(smap.size() / 2);
-  out->nzb = (int32_t)(zmap.size() / 2);
+  const SetupTable tb = sc.carve.bind(d);
   if (fresh) {
-    OMF_HIP(hipMemsetAsync(out->done, 0, o - o_done, st));  // the arrival counters, gz and gh
-    OMF_HIP(hipMemcpyAsync(out->smap, smap.data(), 4 * smap.size(), hipMemcpyHostToDevice, st));
-    OMF_HIP(hipMemcpyAsync(out->supinfo, supinfo.data(), 4 * supinfo.size(), hipMemcpyHostToDevice, st));
-    if (!zmap.empty())
-      OMF_HIP(hipMemcpyAsync(out->zmap, zmap.data(), 4 * zmap.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(topk_setup, dim3(1), dim3(kThreads), 0, st, p->d_sizes, nt, ratio, out->kk,
-                       out->koff, out->tfirst, out->tlast, out->bbase, out->kb2, out->sbase, status, 0u);
-    OMF_HIP(hipGetLastError());
-    OMF_HIP(hipStreamSynchronize(st));  // once per (plan, ratio): the host copy of smap is freed on return
+    OMF_HIP(hipMemsetAsync(tb.done, 0, sc.carve.bytes() - sc.zero_begin, st));  // the arrival counters, gz and gh
+    OMF_HIP(hipMemsetAsync(status, 0, 16, st));
+    auto up = [st](auto* dst, const auto& v) {
+      return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice, st);
+    };
+    OMF_HIP(up(tb.kk, h.kk));
+    OMF_HIP(up(tb.koff, h.koff));
+    OMF_HIP(up(tb.kb2, h.kb2));
+    OMF_HIP(up(tb.tfirst, h.tfirst));
+    OMF_HIP(up(tb.tlast, h.tlast));
+    OMF_HIP(up(tb.bbase, h.bbase));
+    OMF_HIP(up(tb.sbase, h.sbase));
+    OMF_HIP(up(tb.smap, h.smap));
+    OMF_HIP(up(tb.supinfo, h.supinfo));
+    OMF_HIP(up(tb.zmap, h.zmap));
+    OMF_HIP(hipStreamSynchronize(st));  // once per (plan, ratio, sample size)
   }
+  es.dev = tb;
+  es.ratio_bits = bits;
+  es.max_runs = max_runs;
+  es.valid = true;
   return OMF_OK;
 }
 
@@ -2900,10 +2608,7 @@ int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uin
 
 extern "C" {
 
-int64_t omf_topk_k(int64_t numel, double ratio) {
-  int64_t k = (int64_t)((double)numel * ratio);
-  return k < 1 ? 1 : k;
-}
+int64_t omf_topk_k(int64_t numel, double ratio) { return topk_k(numel, ratio); }
 
 int omf_plan_set_topk(omf_plan* plan, int32_t groups, int32_t force_fallback, int64_t sample_runs, float sure_z,
                       float sure_c) {
@@ -2946,7 +2651,7 @@ int omf_topk_stats(omf_plan* plan, int64_t* out6, int32_t reset) {
 size_t omf_topk_workspace_bytes(const omf_plan* plan, double ratio) {
   (void)ratio;
   if (!plan) return 0;
-  return layout(plan).total;
+  return encode_ws(plan).total;
 }
 
 int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t residual_mode, double ratio, float alpha,
@@ -2967,44 +2672,12 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
   if (plan->arena_end > 0xffffffffLL) return fail(OMF_EINVAL, "arena too large for the sort");
   if (((uintptr_t)x & 15) || (residual && ((uintptr_t)residual & 15)))
     return fail(OMF_EINVAL, "x and residual must be 16-byte aligned");
-  const WsLayout L = layout(plan);
+  const EncodeWsLayout& L = encode_ws(plan);
   if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
   DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
-  uint8_t* w = static_cast<uint8_t*>(ws);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(w + L.hist);
-  uint32_t* bin = reinterpret_cast<uint32_t*>(w + L.bin);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(w + L.cnt);
-  uint32_t* flag = reinterpret_cast<uint32_t*>(w + L.flag);
-  uint32_t* status = reinterpret_cast<uint32_t*>(w + L.status);
-  uint32_t* tkey = reinterpret_cast<uint32_t*>(w + L.tkey);
-  uint32_t* zcnt = reinterpret_cast<uint32_t*>(w + L.zcnt);
-  int64_t* koff = reinterpret_cast<int64_t*>(w + L.koff);
-  int64_t* kk = reinterpret_cast<int64_t*>(w + L.kk);
-  uint32_t* tfirst = reinterpret_cast<uint32_t*>(w + L.tfirst);
-  uint32_t* tlast = reinterpret_cast<uint32_t*>(w + L.tlast);
-  uint32_t* seg_b = reinterpret_cast<uint32_t*>(w + L.seg_b);
-  uint32_t* seg_e = reinterpret_cast<uint32_t*>(w + L.seg_e);
-  int64_t* cstart = reinterpret_cast<int64_t*>(w + L.cstart);
-  uint32_t* sub_cnt = reinterpret_cast<uint32_t*>(w + L.sub_cnt);
-  uint32_t* item_cnt = reinterpret_cast<uint32_t*>(w + L.item_cnt);
-  uint32_t* item_off = reinterpret_cast<uint32_t*>(w + L.item_off);
-  uint64_t* cand = reinterpret_cast<uint64_t*>(w + L.cand);
-  uint64_t* sorted = reinterpret_cast<uint64_t*>(w + L.sorted);
-  uint32_t* bbase = reinterpret_cast<uint32_t*>(w + L.bbase);
-  uint32_t* sbase = reinterpret_cast<uint32_t*>(w + L.sbase);
-  int64_t* kb2 = reinterpret_cast<int64_t*>(w + L.kb2);
-  uint32_t* fmap = reinterpret_cast<uint32_t*>(w + L.fmap);
-  uint32_t* tlo = reinterpret_cast<uint32_t*>(w + L.tlo);
-  uint32_t* thi = reinterpret_cast<uint32_t*>(w + L.thi);
-  uint32_t* fcount = reinterpret_cast<uint32_t*>(w + L.fcount);
-  uint32_t* fhist = reinterpret_cast<uint32_t*>(w + L.fhist);
-  int32_t* fbucket = reinterpret_cast<int32_t*>(w + L.fbucket);
-  uint32_t* fse = reinterpret_cast<uint32_t*>(w + L.fse);
-  uint32_t* bstart = reinterpret_cast<uint32_t*>(w + L.bstart);
-  BucketRec* brec = reinterpret_cast<BucketRec*>(w + L.brec);
-  uint32_t* bfill = reinterpret_cast<uint32_t*>(w + L.bfill);
+  const EncodeWs w = L.carve.bind(ws);
   const int32_t nt = plan->nt;
   const int64_t n_items = plan->n_flat;
   const Item* items = plan->d_flat;
@@ -3017,24 +2690,22 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
   const dim3 grid((unsigned)n_items), blk(kThreads);
 
   const bool glob = global_path(plan);
-  if (!glob) OMF_HIP(hipMemsetAsync(w, 0, L.zero_end, st));
+  if (!glob) OMF_HIP(hipMemsetAsync(ws, 0, L.zero_end, st));
   HostSync* hsync = host_sync(plan->device);
   if (!hsync) return fail(OMF_EHIP, "omf_topk_encode: device index out of range");
-  // the per-(plan, ratio) constant tables: made by topk_setup on the first call at this ratio
-  SetupTable tb;
+  // the per-(plan, ratio) constant tables: built and uploaded on the first call at this ratio
+  const EncodeSetup* es = nullptr;
   const TopkKnobs& kn = knobs(plan);
   TopkStats& stats = plan->topk_knobs.stats;
   const int64_t max_runs = sample_max_runs(kn);
   const float2 sure_zc = sure_margin(kn);
-  if (int r = setup_table(plan, ratio, max_runs, st, status, &tb)) return r;
-  kk = tb.kk; koff = tb.koff; tfirst = tb.tfirst; tlast = tb.tlast; bbase = tb.bbase; kb2 = tb.kb2; sbase = tb.sbase;
-  size_t tmp_bytes = L.tmp_bytes;
+  if (int r = setup_table(plan, ratio, max_runs, st, w.status, &es)) return r;
+  const SetupTable& tb = es->dev;
   if (glob) {
     unsigned long long* dstats = device_stats(plan, st);
     if (!dstats) return fail(OMF_ENOMEM, "omf_topk_encode: counter table allocation failed");
     const bool forced = kn.force_fallback != 0;
-    const std::vector<Group> groups = make_groups(plan->sizes, ratio, max_runs,
-                                                  topk_group_count(plan, kn));
+    const std::vector<Group> groups = make_groups(es->host, topk_group_count(plan, kn));
     if (groups.size() > 1)
       if (int r = pipe_streams(hsync)) return r;
     const int dbg = kn.dbg;
@@ -3047,12 +2718,14 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
       if (G.nsb) {
         if (residual_mode == 1)
           hipLaunchKernelGGL((topk_sample<1>), dim3(G.nsb), sblk, 0, s, x, residual, alpha, d_begins, d_sizes,
-                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, status, kk, tfirst, tlast, tkey,
-                             hist, item_cnt, thi, fmap, tlo, fcount, fhist, G.sb0, sure_zc);
+                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, w.status, tb.kk, tb.tfirst,
+                             tb.tlast, w.tkey, w.hist, w.item_cnt, w.thi, w.fmap, w.tlo, w.fcount, w.fhist, G.sb0,
+                             sure_zc);
         else
           hipLaunchKernelGGL((topk_sample<0>), dim3(G.nsb), sblk, 0, s, x, residual, alpha, d_begins, d_sizes,
-                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, status, kk, tfirst, tlast, tkey,
-                             hist, item_cnt, thi, fmap, tlo, fcount, fhist, G.sb0, sure_zc);
+                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, w.status, tb.kk, tb.tfirst,
+                             tb.tlast, w.tkey, w.hist, w.item_cnt, w.thi, w.fmap, w.tlo, w.fcount, w.fhist, G.sb0,
+                             sure_zc);
       }
       if (gi == 0 && groups.size() > 1) {
         OMF_HIP(hipEventRecord(hsync->fork, st));
@@ -3064,42 +2737,44 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
       if (gi > 0) OMF_HIP(hipStreamWaitEvent(s, hsync->fused[(gi - 1) & 1], 0));
       const dim3 fgrid(G.nsub);
       if (residual_mode == 1)
-        hipLaunchKernelGGL((topk_fused<1>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins, tkey, thi, sub_cnt,
-                           item_cnt, cand, G.sub0);
+        hipLaunchKernelGGL((topk_fused<1>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
+                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
       else if (residual_mode == 2)
-        hipLaunchKernelGGL((topk_fused<2>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins, tkey, thi, sub_cnt,
-                           item_cnt, cand, G.sub0);
+        hipLaunchKernelGGL((topk_fused<2>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
+                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
       else
-        hipLaunchKernelGGL((topk_fused<0>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins, tkey, thi, sub_cnt,
-                           item_cnt, cand, G.sub0);
+        hipLaunchKernelGGL((topk_fused<0>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
+                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
       if (groups.size() > 1) OMF_HIP(hipEventRecord(hsync->fused[gi & 1], s));
       // fast path: exact fine-bin histograms, bucket plan
       const dim3 supgrid(G.nsup), supblk(1024);
-      hipLaunchKernelGGL(topk_fine_hist, supgrid, supblk, 0, s, cand, items, sub_cnt, (const uint4*)tb.supinfo, fmap,
-                         tlo, fcount, fhist, bbase, bfill, G.sup0);
+      hipLaunchKernelGGL(topk_fine_hist, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt, (const uint4*)tb.supinfo, w.fmap,
+                         w.tlo, w.fcount, w.fhist, tb.bbase, w.bfill, G.sup0);
       // the plan writes the verdict words (status); the bucket kernels behind it do nothing on a
       // fallback verdict, which the exact tail then handles
       const bool small = G.nb_max <= kScatterSmallB && kn.scatter_small;
       if (!forced && small && kn.planned_scatter)  // the plan inside the scatter launch
-        hipLaunchKernelGGL(topk_scatter_planned, supgrid, supblk, 0, s, cand, items, sub_cnt, (const uint4*)tb.supinfo,
-                           fmap, tlo, fcount, fhist, kk, tkey, bbase, brec, bfill, kb2, d_begins, rz, sorted, flag, zcnt,
-                           status, thi, G.sup0);
+        hipLaunchKernelGGL(topk_scatter_planned, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt,
+                           (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fhist, tb.kk, w.tkey, tb.bbase, w.brec,
+                           w.bfill, tb.kb2, d_begins, rz, w.sorted, w.flag, w.zcnt, w.status, w.thi, G.sup0);
       else
-        hipLaunchKernelGGL(topk_plan, dim3((unsigned)(G.t1 - G.t0)), sblk, 0, s, kk, fcount, fhist, bbase, fbucket,
-                           bstart, brec, bfill, kb2, flag, status, fse, tkey, zcnt, dbg, G.t0);
+        hipLaunchKernelGGL(topk_plan, dim3((unsigned)(G.t1 - G.t0)), sblk, 0, s, tb.kk, w.fcount, w.fhist, tb.bbase,
+                           w.fbucket, w.bstart, w.brec, w.bfill, tb.kb2, w.flag, w.status, w.fse, w.tkey, w.zcnt, dbg,
+                           G.t0);
       if (!forced) {
         if (!(small && kn.planned_scatter)) {  // (the planned scatter has run above)
           if (small)
-            hipLaunchKernelGGL(topk_bucket_scatter<true>, supgrid, supblk, 0, s, cand, items, sub_cnt,
-                               (const uint4*)tb.supinfo, fmap, tlo, fcount, fbucket, bbase, bstart, bfill, kb2,
-                               d_begins, rz, sorted, status, thi, G.sup0);
+            hipLaunchKernelGGL(topk_bucket_scatter<true>, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt,
+                               (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fbucket, tb.bbase, w.bstart,
+                               w.bfill, tb.kb2, d_begins, rz, w.sorted, w.status, w.thi, G.sup0);
           else
-            hipLaunchKernelGGL(topk_bucket_scatter<false>, supgrid, supblk, 0, s, cand, items, sub_cnt,
-                               (const uint4*)tb.supinfo, fmap, tlo, fcount, fbucket, bbase, bstart, bfill, kb2,
-                               d_begins, rz, sorted, status, thi, G.sup0);
+            hipLaunchKernelGGL(topk_bucket_scatter<false>, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt,
+                               (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fbucket, tb.bbase, w.bstart,
+                               w.bfill, tb.kb2, d_begins, rz, w.sorted, w.status, w.thi, G.sup0);
         }
-        hipLaunchKernelGGL(topk_bucket_sort, dim3(G.nbk), dim3(kBT), 0, s, sorted, brec, kk, koff, d_begins, d_sizes,
-                           rz, values, indices, status, fmap, tlo, fcount, fhist, fse, thi, dbg, G.bk0);
+        hipLaunchKernelGGL(topk_bucket_sort, dim3(G.nbk), dim3(kBT), 0, s, w.sorted, w.brec, tb.kk, tb.koff, d_begins,
+                           d_sizes, rz, values, indices, w.status, w.fmap, w.tlo, w.fcount, w.fhist, w.fse, w.thi, dbg,
+                           G.bk0);
       }
       OMF_HIP(hipGetLastError());
     }
@@ -3119,55 +2794,55 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
     ta.nt = nt;
     ta.forced = forced ? 1 : 0;
     ta.skip_arrival = kn.force_fallback == 2 ? 1 : 0;
-    ta.kk = kk;
-    ta.koff = koff;
+    ta.kk = tb.kk;
+    ta.koff = tb.koff;
     ta.tbegin = d_begins;
-    ta.tfirst = tfirst;
-    ta.tlast = tlast;
-    ta.sub_cnt = sub_cnt;
-    ta.item_cnt = item_cnt;
-    ta.item_off = item_off;
-    ta.cnt = cnt;
-    ta.flag = flag;
-    ta.hist = hist;
-    ta.bin = bin;
-    ta.cstart = cstart;
-    ta.cand = cand;
-    ta.packed = sorted;
-    ta.gh = reinterpret_cast<uint32_t*>(w + L.tmp);
-    ta.status = status;
+    ta.tfirst = tb.tfirst;
+    ta.tlast = tb.tlast;
+    ta.sub_cnt = w.sub_cnt;
+    ta.item_cnt = w.item_cnt;
+    ta.item_off = w.item_off;
+    ta.cnt = w.cnt;
+    ta.flag = w.flag;
+    ta.hist = w.hist;
+    ta.bin = w.bin;
+    ta.cstart = w.cstart;
+    ta.cand = w.cand;
+    ta.packed = w.sorted;
+    ta.gh = reinterpret_cast<uint32_t*>(w.tmp);
+    ta.status = w.status;
     ta.values = values;
     ta.indices = indices;
     ta.stats = dstats;
     ta.err = plan->err_word();
     ta.zmap = (const uint2*)tb.zmap;
-    ta.nzc = (uint32_t)tb.nzb;
-    ta.zcnt = zcnt;
+    ta.nzc = (uint32_t)es->host.nzb;
+    ta.zcnt = w.zcnt;
     ta.tsize = d_sizes;
     hipLaunchKernelGGL(topk_exact_tail, dim3(tail_grid(plan->device)), dim3(kThreads), 0, st, ta);
     OMF_HIP(hipGetLastError());
-    (void)tmp_bytes;
     return OMF_OK;
   } else {
     ++stats.exact;
     if (residual_mode == 0)
-      hipLaunchKernelGGL((topk_prep_hist<0>), grid, blk, 0, st, x, residual, alpha, items, hist);
+      hipLaunchKernelGGL((topk_prep_hist<0>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
     else if (residual_mode == 1)
-      hipLaunchKernelGGL((topk_prep_hist<1>), grid, blk, 0, st, x, residual, alpha, items, hist);
+      hipLaunchKernelGGL((topk_prep_hist<1>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
     else
-      hipLaunchKernelGGL((topk_prep_hist<2>), grid, blk, 0, st, x, residual, alpha, items, hist);
-    hipLaunchKernelGGL(topk_select_bin, dim3((unsigned)nt), blk, 0, st, hist, kk, bin);
-    hipLaunchKernelGGL(topk_collect, grid, blk, 0, st, tp, scale, items, d_begins, bin, cnt, cand);
-    hipLaunchKernelGGL(topk_segments, dim3(((unsigned)nt + kThreads - 1) / kThreads), blk, 0, st, nt, d_begins, cnt,
-                       seg_b, seg_e);
+      hipLaunchKernelGGL((topk_prep_hist<2>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
+    hipLaunchKernelGGL(topk_select_bin, dim3((unsigned)nt), blk, 0, st, w.hist, tb.kk, w.bin);
+    hipLaunchKernelGGL(topk_collect, grid, blk, 0, st, tp, scale, items, d_begins, w.bin, w.cnt, w.cand);
+    hipLaunchKernelGGL(topk_segments, dim3(((unsigned)nt + kThreads - 1) / kThreads), blk, 0, st, nt, d_begins, w.cnt,
+                       w.seg_b, w.seg_e);
     OMF_HIP(hipGetLastError());
-    OMF_HIP(rocprim::segmented_radix_sort_keys_desc(w + L.tmp, tmp_bytes, cand, sorted,
+    size_t tmp_bytes = L.tmp_bytes;
+    OMF_HIP(rocprim::segmented_radix_sort_keys_desc(w.tmp, tmp_bytes, w.cand, w.sorted,
                                                     (unsigned int)plan->arena_end, (unsigned int)nt,
-                                                    seg_b, seg_e, 0, 64, st, false));
+                                                    w.seg_b, w.seg_e, 0, 64, st, false));
   }
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((kmax + kThreads - 1) / kThreads, 1024));
-  hipLaunchKernelGGL(topk_gather, dim3(gx, (unsigned)nt), blk, 0, st, tp, scale, rz, sorted, d_begins, d_sizes, kk,
-                     koff, values, indices);
+  hipLaunchKernelGGL(topk_gather, dim3(gx, (unsigned)nt), blk, 0, st, tp, scale, rz, w.sorted, d_begins, d_sizes,
+                     tb.kk, tb.koff, values, indices);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
 }
@@ -3354,7 +3029,7 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
     if (k > sizes[t]) return fail(OMF_EINVAL, "selected index k out of range (k > numel): compress_ratio too large");
     K[t + 1] = K[t] + k;
   }
-  const WsLayout L = layout(plan);
+  const EncodeWsLayout& L = encode_ws(plan);
   if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
   if (n_reordered) *n_reordered = 0;
   if (nt == 0) return OMF_OK;
@@ -3362,12 +3037,11 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   DeviceGuard g(dev);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
-  uint8_t* w = static_cast<uint8_t*>(ws);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(w + L.cnt);  // the encode's scratch, free once it is done
-  uint32_t* flags = reinterpret_cast<uint32_t*>(w + L.flag);
-  SetupTable tb;
-  if (int r = setup_table(plan, ratio, sample_max_runs(knobs(plan)), st, reinterpret_cast<uint32_t*>(w + L.status), &tb))
-    return r;
+  const EncodeWs w = L.carve.bind(ws);
+  uint32_t *cnt = w.cnt, *flags = w.flag;  // the encode's scratch, free once it is done
+  const EncodeSetup* es = nullptr;
+  if (int r = setup_table(plan, ratio, sample_max_runs(knobs(plan)), st, w.status, &es)) return r;
+  const SetupTable& tb = es->dev;
   const int64_t n_items = plan->n_flat;
   const Item* items = plan->d_flat;
   const bool ef = residual_mode != 0;
@@ -3440,16 +3114,11 @@ int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_
   return OMF_OK;
 }
 
-// Whole-arena decode.  Plan-owned constant tables per selection layout (omf_plan.h 
-// topk_table, keyed by the ratio; topk_table_counts, keyed by a received message's per-tensor
-// counts): koff[nt + 1] (int64: each tensor's first value), cap_base[nsuper + 1] (uint32: the
-// tiled decode's bucket-capacity prefix) and blk_t (per place block: its first and last tensor).
-// Caller workspace of the tiled zero-fill decode: fill[nsuper] + the overflow count (left zero by
-// every call), the buckets (cap_base[nsuper] entries) and the overflow list (ktot).
+// Whole-arena decode.  Plan-owned constant tables per selection layout (omf_plan.h topk_table, keyed
+// by the ratio; topk_table_counts, keyed by a received message's per-tensor counts) and the caller
+// workspace of the tiled zero-fill decode: topk_layout's DecodeTables / DecTable / DecWs.
 struct DecTables {
-  int64_t* koff = nullptr;
-  uint32_t* cap_base = nullptr;
-  uint32_t* blk_t = nullptr;  // per place block: its first and last tensor
+  DecTable dev{};
   int32_t nsuper = 0;
   uint64_t cap_total = 0;
 };
@@ -3480,63 +3149,6 @@ static int check_counts(const omf_plan* plan, const int64_t* counts, int64_t* kt
   return OMF_OK;
 }
 
-// Host computation of the tables (also sizes the workspace): bucket capacity = 2 x the
-// expected count of the super-tile (each tensor's k spread over its elements) + 256.
-static int64_t dec_place_blocks(int64_t ktot) { return std::max<int64_t>(1, (ktot + kDecChunk - 1) / kDecChunk); }
-
-static void dec_tables_host(const omf_plan* p, const int64_t* ks, std::vector<int64_t>& koff,
-                            std::vector<uint32_t>& cap_base, int32_t& nsuper, std::vector<uint32_t>* blk_t = nullptr) {
-  const std::vector<int64_t>& sizes = p->sizes;
-  const int32_t nt = (int32_t)sizes.size();
-  const int64_t ae = p->arena_end;
-  nsuper = (int32_t)((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits);
-  koff.assign((size_t)nt + 1, 0);
-  std::vector<double> expect((size_t)nsuper, 0.0);
-  const std::vector<int64_t>& begins = p->offsets;
-  for (int32_t t = 0; t < nt; ++t) {
-    const int64_t n = sizes[t], k = ks[t];
-    koff[(size_t)t + 1] = koff[(size_t)t] + k;
-    if (n <= 0 || k <= 0) continue;
-    const int64_t begin = begins[t];
-    const double dens = (double)k / (double)n;
-    for (int64_t s0 = begin >> kDecSuperBits; s0 <= (begin + n - 1) >> kDecSuperBits; ++s0) {
-      const int64_t lo = std::max(begin, s0 << kDecSuperBits), hi = std::min(begin + n, (s0 + 1) << kDecSuperBits);
-      expect[(size_t)s0] += dens * (double)(hi - lo);
-    }
-  }
-  cap_base.assign((size_t)nsuper + 1, 0);
-  for (int32_t q = 0; q < nsuper; ++q) {
-    const uint64_t cap = std::min<uint64_t>((uint64_t)std::ceil(2.0 * expect[(size_t)q]) + 256, (uint64_t)1 << kDecSuperBits);
-    cap_base[(size_t)q + 1] = cap_base[(size_t)q] + (uint32_t)cap;
-  }
-  if (blk_t) {  // the largest t with koff[t] <= j, as dec_tensor_of
-    const int64_t ktot = koff[(size_t)nt];
-    const int64_t nb = dec_place_blocks(ktot);
-    blk_t->assign(2 * (size_t)nb, 0);
-    auto tensor_of = [&](int64_t j) {
-      return (uint32_t)(std::upper_bound(koff.begin(), koff.begin() + nt, j) - koff.begin() - 1);
-    };
-    for (int64_t b = 0; b < nb; ++b) {
-      const int64_t j0 = b * kDecChunk, j1 = std::max<int64_t>(std::min<int64_t>(j0 + kDecChunk, ktot), j0 + 1);
-      (*blk_t)[2 * (size_t)b] = tensor_of(j0);
-      (*blk_t)[2 * (size_t)b + 1] = tensor_of(j1 - 1);
-    }
-  }
-}
-
-struct DecWs {
-  size_t fill, pairs, ovf, total;
-};
-static DecWs dec_ws_layout(int32_t nsuper, uint64_t cap_total, int64_t ktot) {
-  DecWs d;
-  size_t o = 0;
-  d.fill = o; o = align256(o + 4 * ((size_t)nsuper + 1));  // + the overflow count
-  d.pairs = o; o = align256(o + 8 * (size_t)std::max<uint64_t>(cap_total, 1));
-  d.ovf = o; o = align256(o + 8 * (size_t)std::max<int64_t>(ktot, 1));
-  d.total = o;
-  return d;
-}
-
 static uint64_t ratio_key(double ratio) {
   uint64_t k;
   std::memcpy(&k, &ratio, 8);
@@ -3546,41 +3158,28 @@ static uint64_t ratio_key(double ratio) {
 // The plan's tables for the layout ks (computed and uploaded on first use; the bucket total is
 // kept in the table's host word).  ratio != NULL: keyed by the ratio, else by the counts.
 static int dec_tables(omf_plan* p, const int64_t* ks, int64_t ktot, const double* ratio, DecTables* out) {
-  const int32_t nt = p->nt;
-  const int64_t ae = p->arena_end;
-  const int32_t nsuper = (int32_t)((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits);
-  const int64_t nb = dec_place_blocks(ktot);
-  const size_t o_cap = align256(8 * ((size_t)nt + 1)), o_blk = o_cap + align256(4 * ((size_t)nsuper + 1));
-  const size_t bytes = o_blk + 8 * (size_t)nb;
+  out->nsuper = dec_nsuper(p->arena_end);
+  const Carve<DecTable> carve = dec_table_carve(p->nt, out->nsuper, dec_place_blocks(ktot));
   bool fresh = false;
   uint64_t* host = nullptr;
-  void* d = ratio ? topk_table(p, ratio_key(*ratio), bytes, &fresh, &host)
-                  : topk_table_counts(p, ks, bytes, &fresh, &host);
+  void* d = ratio ? topk_table(p, ratio_key(*ratio), carve.bytes(), &fresh, &host)
+                  : topk_table_counts(p, ks, carve.bytes(), &fresh, &host);
   if (!d) return fail(OMF_ENOMEM, "Top-K decode: table allocation failed");
-  out->koff = static_cast<int64_t*>(d);
-  out->cap_base = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d) + o_cap);
-  out->blk_t = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d) + o_blk);
-  out->nsuper = nsuper;
+  out->dev = carve.bind(d);
   if (fresh) {
-    std::vector<int64_t> koff;
-    std::vector<uint32_t> cap_base, blk_t;
-    int32_t ns = 0;
-    dec_tables_host(p, ks, koff, cap_base, ns, &blk_t);
-    OMF_HIP(hipMemcpy(out->koff, koff.data(), 8 * koff.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->cap_base, cap_base.data(), 4 * cap_base.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->blk_t, blk_t.data(), 4 * blk_t.size(), hipMemcpyHostToDevice));
-    *host = cap_base.back();
+    const DecodeTables h = dec_tables_host(p->sizes, p->offsets, p->arena_end, ks);
+    OMF_HIP(hipMemcpy(out->dev.koff, h.koff.data(), 8 * h.koff.size(), hipMemcpyHostToDevice));
+    OMF_HIP(hipMemcpy(out->dev.cap_base, h.cap_base.data(), 4 * h.cap_base.size(), hipMemcpyHostToDevice));
+    OMF_HIP(hipMemcpy(out->dev.blk_t, h.blk_t.data(), 4 * h.blk_t.size(), hipMemcpyHostToDevice));
+    *host = h.cap_base.back();
   }
   out->cap_total = *host;
   return OMF_OK;
 }
 
 static size_t dec_ws_bytes(const omf_plan* plan, const int64_t* ks, int64_t ktot) {
-  std::vector<int64_t> koff;
-  std::vector<uint32_t> cap_base;
-  int32_t nsuper = 0;
-  dec_tables_host(plan, ks, koff, cap_base, nsuper);
-  return dec_ws_layout(nsuper, cap_base.back(), ktot).total;
+  const DecodeTables h = dec_tables_host(plan->sizes, plan->offsets, plan->arena_end, ks);
+  return dec_ws_layout(h.nsuper, h.cap_base.back(), ktot).bytes();
 }
 
 // One client's whole selection in the layout ks into the arena y (modes 0 / 1 / 2).
@@ -3596,27 +3195,25 @@ static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const 
   const int64_t ae = plan->arena_end;
   DecTables tb;
   if (int r = dec_tables(plan, ks, ktot, ratio, &tb)) return r;
-  if (mode == 0 && ws && ((ae + (1 << kDecSuperBits) - 1) >> kDecSuperBits) <= kDecMaxSuper) {
+  if (mode == 0 && ws && tb.nsuper <= kDecMaxSuper) {
     // one streaming write of the arena (larger arenas: fill + scatter below)
-    const DecWs d = dec_ws_layout(tb.nsuper, tb.cap_total, ktot);
-    if (ws_bytes < d.total) return fail(OMF_EINVAL, "Top-K arena decode: workspace too small");
+    const Carve<DecWs> d = dec_ws_layout(tb.nsuper, tb.cap_total, ktot);
+    if (ws_bytes < d.bytes()) return fail(OMF_EINVAL, "Top-K arena decode: workspace too small");
     if (((uintptr_t)ws & 255) || ((uintptr_t)y & 15)) return fail(OMF_EINVAL, "Top-K arena decode: misaligned buffer");
-    uint8_t* w = static_cast<uint8_t*>(ws);
-    uint32_t* fill = reinterpret_cast<uint32_t*>(w + d.fill);
-    uint32_t* ovf_cnt = fill + tb.nsuper;
-    uint64_t* pairs = reinterpret_cast<uint64_t*>(w + d.pairs);
-    uint64_t* ovf = reinterpret_cast<uint64_t*>(w + d.ovf);
+    const DecWs w = d.bind(ws);
+    uint32_t *fill = w.fill, *ovf_cnt = fill + tb.nsuper;
+    uint64_t *pairs = w.pairs, *ovf = w.ovf;
     // fill[] and the overflow count start at zero (a zero-filled workspace) and every call leaves
     // them so: topk_dec_tiles clears its bucket's count, topk_dec_overflow the overflow count (a
     // memset here was two fill kernels, ~10 us per decode)
     if (ktot > 0) {
       const dim3 gb((unsigned)dec_place_blocks(ktot));
       hipLaunchKernelGGL(topk_dec_place, gb, dim3(kThreads), 4 * (size_t)tb.nsuper, st, values, indices,
-                         plan->d_sizes, plan->d_begins, (const int64_t*)tb.koff,
-                         (const uint32_t*)tb.blk_t, ktot, (const uint32_t*)tb.cap_base, fill, pairs, ovf_cnt, ovf);
+                         plan->d_sizes, plan->d_begins, (const int64_t*)tb.dev.koff, (const uint32_t*)tb.dev.blk_t,
+                         ktot, (const uint32_t*)tb.dev.cap_base, fill, pairs, ovf_cnt, ovf);
     }
     hipLaunchKernelGGL(topk_dec_tiles, dim3((unsigned)tb.nsuper), dim3(kDecTileThreads), 0, st, (const uint64_t*)pairs,
-                       (const uint32_t*)tb.cap_base, fill, y, ae);
+                       (const uint32_t*)tb.dev.cap_base, fill, y, ae);
     if (ktot > 0) hipLaunchKernelGGL(topk_dec_overflow, dim3(1), dim3(kThreads), 0, st, ovf_cnt, (const uint64_t*)ovf, y);
     OMF_HIP(hipGetLastError());
     return OMF_OK;
@@ -3625,7 +3222,7 @@ static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const 
   if (ktot == 0) return OMF_OK;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 4096));
   hipLaunchKernelGGL(topk_scatter_arena, dim3(gx), dim3(kThreads), 0, st, values, indices,
-                     plan->d_sizes, plan->d_begins, (const int64_t*)tb.koff, (int)nt,
+                     plan->d_sizes, plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt,
                      ktot, y, mode == 2 ? 1 : 0);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
@@ -3689,7 +3286,7 @@ int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indic
   if (ktot == 0) return OMF_OK;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + 4 * kThreads - 1) / (4 * kThreads), 2048));
   hipLaunchKernelGGL(topk_check_idx, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     (const int64_t*)tb.koff, (int)nt, ktot, bad);
+                     (const int64_t*)tb.dev.koff, (int)nt, ktot, bad);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
 }
@@ -3722,9 +3319,9 @@ int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64
   if (fresh) OMF_HIP(hipMemsetAsync(bits, 0, 4 * words, st));
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 2048));
   hipLaunchKernelGGL(topk_dup_bits<true>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     plan->d_begins, (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
+                     plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt, ktot, bits, flags);
   hipLaunchKernelGGL(topk_dup_bits<false>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     plan->d_begins, (const int64_t*)tb.koff, (int)nt, ktot, bits, flags);
+                     plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt, ktot, bits, flags);
   OMF_HIP(hipGetLastError());
   return plan_leave(plan, st);
 }
