@@ -1,7 +1,8 @@
 // omf_plan.h — internal definition of the plan behind the C ABI's opaque omf_plan.
 //
 // Not part of the C ABI.  omf_qsgd.hip creates, uploads and destroys a plan and launches the QSGD
-// kernels from it; omf_qsgd_pack.hip and omf_topk.hip read its arena tables and keep their
+// kernels from it (the bracketed encoder's: omf_qsgd_bracket.hip, which also makes that encoder's lazy
+// buffers); omf_qsgd_pack.hip and omf_topk.hip read its arena tables and keep their
 // per-plan device tables in it.  The host tables come from omf_plan_layout.h; Top-K's host state
 // (its workspace layout, made at the plan's first Top-K use, and its latest encode tables) is
 // omf_topk_layout.h's.
@@ -111,7 +112,8 @@ struct omf_plan {
   int32_t spec_wide = 1;  // wide levels (5-8 bits, fp32) through the bracket (1) or as before (0): OMF_SPEC_WIDE
   int32_t spec_last_pw = 0;  // the list capacity of the latest bracketed encode
   // ---- buffers made at the first encode that needs them (ensure_wide / ensure_fused_bracket in
-  // omf_qsgd.hip): all of a group's pointers are set or none; d_lazy owns the allocations
+  // omf_qsgd_bracket.hip, through make_buffers of omf_qsgd.hip): all of a group's pointers are set or
+  // none; d_lazy owns the allocations
   std::vector<void*> d_lazy;
   uint32_t* d_spec_slots_w = nullptr;  // wide levels (bit widths 5-8): slots and records of the wide
   float4* d_spec_recs_w = nullptr;     // list capacity,

@@ -3,7 +3,8 @@
 // plan's one device allocation, and the choice of the encoder that serves a call.
 //
 // Pure integer code: no HIP header, so tests/host/plan_layout_check.cpp runs it on a CPU under
-// sanitizers.  omf_qsgd.hip uploads what build_tables returns and launches what choose_encoder picks.
+// sanitizers.  omf_qsgd.hip uploads what build_tables returns and launches what choose_encoder picks
+// (the bracketed encoder through omf_bracket.h, the ring through omf_ring.h).
 #pragma once
 
 #include <cstddef>

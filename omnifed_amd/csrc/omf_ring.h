@@ -1,7 +1,8 @@
 // omf_ring.h — internal interface of the single-read QSGD encoder (omf_qsgd_ring.hip).
 //
 // Not part of the C ABI: the plan (omf_qsgd.hip) uploads the work-item tables that
-// omf_plan_layout.cpp builds and calls omf::ring::launch.  DESIGN.md §3.1 describes the algorithm.
+// omf_plan_layout.cpp builds and calls omf::ring::launch (as it calls omf::bracket::launch of
+// omf_bracket.h for the bracketed encoder).  DESIGN.md §3.1 describes the algorithm.
 #pragma once
 
 #include "omf_common.h"

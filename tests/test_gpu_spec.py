@@ -1,4 +1,4 @@
-"""Bracketed single-read encoder (strategy 3, omf_qsgd.hip qsgd_spec_*) against the oracle.
+"""Bracketed single-read encoder (strategy 3, omf_qsgd_bracket.hip qsgd_spec_*) against the oracle.
 
 Every payload is compared bit for bit with the oracle's QSGD quantiser given the encoder's own
 norm (checked against fp64 at NORM_RTOL) and the Philox uniforms of oracle/philox.py — the bar

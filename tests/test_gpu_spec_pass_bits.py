@@ -1,4 +1,4 @@
-"""The bracketed pass's bits (omf_qsgd.hip qsgd_spec_quant*, qsgd_spec_finish) across a rewrite of
+"""The bracketed pass's bits (omf_qsgd_bracket.hip qsgd_spec_quant*, qsgd_spec_finish) across a rewrite of
 its instruction schedule, wave reduction and integer paths.
 
 * Norms and payload against ``tests/golden/spec_parent_bits.npz``: ``norm_out`` (bit patterns) and
