@@ -2,8 +2,9 @@
 //
 // Not part of the C ABI.  omf_qsgd.hip creates, uploads and destroys a plan and launches the QSGD
 // kernels from it (the bracketed encoder's: omf_qsgd_bracket.hip, which also makes that encoder's lazy
-// buffers); omf_qsgd_pack.hip and omf_topk.hip read its arena tables and keep their
-// per-plan device tables in it.  The host tables come from omf_plan_layout.h; Top-K's host state
+// buffers); omf_qsgd_pack.hip and the Top-K units (omf_topk.hip the encoder, omf_topk_recv.hip decode and
+// checks, omf_topk_tie.hip the tie rewrite) read its arena tables and keep their per-plan device tables
+// in it.  The host tables come from omf_plan_layout.h; Top-K's host state
 // (its workspace layout, made at the plan's first Top-K use, and its latest encode tables) is
 // omf_topk_layout.h's.
 #pragma once
@@ -122,7 +123,7 @@ struct omf_plan {
   double* d_spec_fb_part = nullptr;    // fused bracket: its parts' partial sums, arrival counters
   uint32_t* d_spec_fb_cnt = nullptr;   // and granules
   uint64_t* d_spec_brgran = nullptr;
-  // Top-K tiled decode: per-ratio constant tables (omf_topk.hip), allocated on first use, with
+  // Top-K tiled decode: per-ratio constant tables (omf_topk_recv.hip), allocated on first use, with
   // one host word each (the table's size facts)
   struct TopkTable {
     uint64_t key;

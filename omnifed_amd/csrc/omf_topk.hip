@@ -32,15 +32,17 @@
 //                       candidate count, a gather.
 // Larger plans take the exact path (histogram of every t', collection, a segmented
 // descending sort of (|t'|bits << 32 | ~index) per tensor).
-// Decode is a scatter (mode 0 zero-fill, 1 overlay, 2 scatter-add); the arena zero-fill decode
-// with a workspace is tiled (topk_dec_place / topk_dec_tiles / topk_dec_overflow).
 //
 // The host side's integer code is omf_topk_layout.{h,cpp} (no HIP header, CPU-tested): the constants
 // shared with the kernels, the per-tensor rules (k, bucket slots, sampling stride, items, super-items:
 // one definition each, called from the kernels too), the encoder's constant tables (built on the host
 // and uploaded once per plan, ratio and sample size), the pipeline groups, the decoder's tables and
-// the carve of both workspaces.  This file keeps the kernels, the launches and what needs the HIP
-// runtime or rocPRIM (the sort's temporary, the CU count).
+// the carve of both workspaces.  This file keeps the encoder's kernels, its launches and what needs
+// the HIP runtime or rocPRIM (the sort's temporary, the CU count).
+//
+// Decode and the checks of a received selection: omf_topk_recv.hip (omf_topk_dev.h holds the search over
+// koff its kernels share with the exact tail's gather).  The torch-order rewrite of a finished selection:
+// omf_topk_tie.hip, which gets this unit's workspace carve and tables by omf::topk_encode_tables.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,19 +51,15 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
-#include <atomic>
-#include <bit>
-#include <chrono>
-#include <memory>
 #include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/omf_codec.h"
 #include "../../include/omf_codec_experimental.h"
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_topk_dev.h"
+#include "omf_topk_enc.h"
 #include "omf_topk_layout.h"
 
 using namespace omf;
@@ -73,7 +71,7 @@ constexpr int kShift = 21;  // key (31 bits) >> 21 -> 10-bit bin (exact path)
 constexpr int kSShift = 31 - kSBits;
 // The threshold bin's margin over the expected k*S/n samples: OMF_THR_Z sigma + OMF_THR_C (a
 // performance knob only — a tensor left with fewer than k candidates takes the exact redo).
-#ifndef OMF_THR_Z  // experiment builds may override them (scripts/exp/tk_thr_ab.sh)
+#ifndef OMF_THR_Z  // -D overrides for a variant library (scripts/exp/variant_lib.sh)
 #define OMF_THR_Z 6.0
 #endif
 #ifndef OMF_THR_C
@@ -86,7 +84,7 @@ static_assert(kSub == (int64_t)kV * kThreads * 4, "a flat item: kV float4 per th
 // gives (tensor ascending, |t'| descending, index ascending): 5 digit passes instead of 8.
 constexpr int kSortBits = 39;
 constexpr int kFineMaxBits = 18;      // a coarse bin splits by at most the rest of the mantissa
-#ifndef OMF_FINE_MARGIN  // experiment builds may override it (scripts/exp/tk_margin_ab.sh)
+#ifndef OMF_FINE_MARGIN  // a -D override for a variant library (scripts/exp/variant_lib.sh)
 #define OMF_FINE_MARGIN 8
 #endif
 constexpr int kFineMargin = OMF_FINE_MARGIN;  // a fine bin expects <= kBucketHalf / 8 elements
@@ -984,27 +982,6 @@ __device__ void topk_plan_tensor(int t, const int64_t* __restrict__ kk, const ui
                                  BucketRec* __restrict__ brec, uint32_t* __restrict__ bfill,
                                  const int64_t* __restrict__ kb2, uint32_t* __restrict__ flag,
                                  uint32_t* __restrict__ status, uint32_t* __restrict__ fse,
-                                 const uint32_t* __restrict__ tkey, uint32_t* __restrict__ zcnt, int dbg);
-__global__ __launch_bounds__(1024) void topk_plan(const int64_t* __restrict__ kk, const uint32_t* __restrict__ fcount,
-                                                  const uint32_t* __restrict__ fhist,
-                                                  const uint32_t* __restrict__ bbase, int32_t* __restrict__ fbucket,
-                                                  uint32_t* __restrict__ bstart, BucketRec* __restrict__ brec,
-                                                  uint32_t* __restrict__ bfill, const int64_t* __restrict__ kb2,
-                                                  uint32_t* __restrict__ flag, uint32_t* __restrict__ status,
-                                                  uint32_t* __restrict__ fse, const uint32_t* __restrict__ tkey,
-                                                  uint32_t* __restrict__ zcnt, int dbg, int32_t t0) {
-  // (the verdict words in status are read by the kernels queued behind: the bucket kernels, the
-  // zero fill and the exact tail — no host round trip)
-  topk_plan_tensor((int)(t0 + blockIdx.x), kk, fcount, fhist, bbase, fbucket, bstart, brec, bfill, kb2, flag, status,
-                   fse, tkey, zcnt, dbg);
-}
-
-__device__ void topk_plan_tensor(int t, const int64_t* __restrict__ kk, const uint32_t* __restrict__ fcount,
-                                 const uint32_t* __restrict__ fhist, const uint32_t* __restrict__ bbase,
-                                 int32_t* __restrict__ fbucket, uint32_t* __restrict__ bstart,
-                                 BucketRec* __restrict__ brec, uint32_t* __restrict__ bfill,
-                                 const int64_t* __restrict__ kb2, uint32_t* __restrict__ flag,
-                                 uint32_t* __restrict__ status, uint32_t* __restrict__ fse,
                                  const uint32_t* __restrict__ tkey, uint32_t* __restrict__ zcnt, int dbg) {
   constexpr int PER = kFineMax / 1024;
   __shared__ uint32_t s_bs[kPlanMaxBuckets];
@@ -1089,6 +1066,20 @@ __device__ void topk_plan_tensor(int t, const int64_t* __restrict__ kk, const ui
     flag[t] = 0;
     if (s_over) atomicOr(&status[2], 1u);
   }
+}
+
+__global__ __launch_bounds__(1024) void topk_plan(const int64_t* __restrict__ kk, const uint32_t* __restrict__ fcount,
+                                                  const uint32_t* __restrict__ fhist,
+                                                  const uint32_t* __restrict__ bbase, int32_t* __restrict__ fbucket,
+                                                  uint32_t* __restrict__ bstart, BucketRec* __restrict__ brec,
+                                                  uint32_t* __restrict__ bfill, const int64_t* __restrict__ kb2,
+                                                  uint32_t* __restrict__ flag, uint32_t* __restrict__ status,
+                                                  uint32_t* __restrict__ fse, const uint32_t* __restrict__ tkey,
+                                                  uint32_t* __restrict__ zcnt, int dbg, int32_t t0) {
+  // (the verdict words in status are read by the kernels queued behind: the bucket kernels, the
+  // zero fill and the exact tail — no host round trip)
+  topk_plan_tensor((int)(t0 + blockIdx.x), kk, fcount, fhist, bbase, fbucket, bstart, brec, bfill, kb2, flag, status,
+                   fse, tkey, zcnt, dbg);
 }
 
 // Fast path, scatter: every kept candidate into its bucket (rank window of the tensor's
@@ -1202,9 +1193,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 // sorted instead.  Sort key: (2^31-1-|t'|bits) << 33 | index << 1 | sign.
 constexpr int kSubBins = kBT * kBI;  // 4096
 constexpr uint32_t kMaxRun = 32;
-#ifndef OMF_SORT_LOCAL  // 1: sub-bins from an LDS histogram of the bucket's keys; 0: from the fine bins
-#define OMF_SORT_LOCAL 1
-#endif
 #ifndef OMF_SORT_WAVES  // waves per SIMD the bucket sort is compiled for (experiment builds may override)
 #define OMF_SORT_WAVES 6
 #endif
@@ -1233,7 +1221,7 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(OMF_SORT_WA
       uint64_t out[kSubBins];
       uint32_t start2[kSubBins / 2];
     } cs;
-    struct {  // OMF_SORT_LOCAL: the level-1 histogram, and the wave min / max (then scan totals)
+    struct {  // the level-1 histogram, and the wave min / max (then scan totals)
       uint32_t h1[kBT];
       uint32_t mm[2 * (kBT / 64)];
     } lv;
@@ -1247,7 +1235,6 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(OMF_SORT_WA
   const int64_t k = kk[t], o = koff[t], base = tbegin[t], n = tsize[t];  // issued with the key loads
   uint64_t keys[kBI];
   uint32_t meta[kBI];  // sub-bin << 16 | slot in it (0xffffffff: no key)
-#if OMF_SORT_LOCAL
   // Sub-bin of a key from the bucket's own keys, in LDS (no memory round after the key loads):
   // the bucket's |t'| range [mmin, mmax] is cut into kBT equal level-1 bins, counted and scanned;
   // a key's sub-bin = its level-1 bin's first rank plus its linear position inside that bin times
@@ -1308,49 +1295,6 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(OMF_SORT_WA
     meta[j] = e < cnt ? min((w & 0xffffu) + in, cnt - 1u) : 0xffffffffu;
     keys[j] = e < cnt ? ((uint64_t)(0x7fffffffu - mag) << 33) | ((keys[j] >> 32) << 1) | (uint64_t)(bits >> 31) : ~0ull;
   }
-#else
-  const uint32_t lo = tlo[t], F = fcount[t], hi = thi[t];
-  const uint32_t* map_t = fmap + (size_t)t * kCoarse;
-  const uint32_t* h_t = fhist + (size_t)t * kFineMax;
-  const uint32_t* se_t = fse + (size_t)t * kFineMax;
-  // Sub-bin of a key = its rank slot if keys were spread evenly inside their fine bin: the fine
-  // bin's first rank in the bucket (se - start) plus (c - 1 - low * c / 2^wbits) for a bin of
-  // c keys, descending |t'|.  Sub-bins = the bucket's key count, about one key each.
-  // Three rounds of loads, each issued whole before any is used (no load under a branch): the
-  // keys (past the count: the last key again), their fine bins' maps, the bins' counts and ranks.
-  uint32_t mv[kBI];  // each key's coarse-bin map entry (its fine bin and low bits follow from it)
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) keys[j] = src[min(threadIdx.x + (uint32_t)j * kBT, cnt - 1u)];  // striped
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) asm volatile("" : "+v"(keys[j]));
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) mv[j] = fine_map_entry((uint32_t)keys[j] & 0x7fffffffu, lo, map_t);
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) asm volatile("" : "+v"(mv[j]));
-  uint32_t cbv[kBI], sev[kBI];
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) {
-    uint32_t low, wb;
-    const uint32_t fb = fine_bin_from((uint32_t)keys[j] & 0x7fffffffu, lo, mv[j], F, low, wb);
-    cbv[j] = h_t[fb];
-    sev[j] = se_t[fb];
-  }
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) asm volatile("" : "+v"(cbv[j]), "+v"(sev[j]));  // loaded here, not sunk under e < cnt
-#pragma unroll
-  for (int j = 0; j < kBI; ++j) {
-    const uint32_t e = threadIdx.x + (uint32_t)j * kBT;
-    const uint32_t cb = cbv[j], rel = sev[j] - st;
-    const uint32_t bits = (uint32_t)keys[j], mag = bits & 0x7fffffffu;
-    uint32_t low, wb;
-    (void)fine_bin_from(mag, lo, mv[j], F, low, wb);
-    const uint32_t in = cb - 1u - (uint32_t)(((uint64_t)low * cb) >> wb);
-    meta[j] = e < cnt ? min(rel + in, cnt - 1u) : 0xffffffffu;
-    keys[j] = e < cnt ? ((uint64_t)(0x7fffffffu - mag) << 33) | ((keys[j] >> 32) << 1) | (uint64_t)(bits >> 31) : ~0ull;
-  }
-  for (int i = threadIdx.x; i < kSubBins / 2; i += kBT) s_u.cs.start2[i] = 0;
-  __syncthreads();
-#endif
 #pragma unroll
   for (int j = 0; j < kBI; ++j) {
     if (meta[j] == 0xffffffffu) continue;
@@ -1459,7 +1403,6 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(OMF_SORT_WA
 // fine bin over kBucketHalf keys, whose keys could run past the tensor's bucket region) places
 // nothing: the call takes the fallback, which restores every candidate's residual.  Blocks of
 // unflagged tensors proceed whatever the others' verdicts (their bucket writes are then unused).
-static_assert(OMF_SORT_LOCAL, "topk_scatter_planned needs the sort that does not read the fine-bin ranks");
 #ifndef OMF_PLANNED_CACHE  // key loads per thread (x4) kept in registers between the scatter's phases
 #define OMF_PLANNED_CACHE 2
 #endif
@@ -1737,18 +1680,6 @@ __global__ __launch_bounds__(kThreads) void topk_gather(const float* __restrict_
   }
 }
 
-// The tensor t with koff[t] <= j < koff[t + 1] among [0, nt): the largest t with koff[t] <= j
-// (a tensor with no values shares its koff with the next one, which is then the larger t).
-__device__ __forceinline__ int koff_tensor(const int64_t* koff, int nt, int64_t j) {
-  int lo = 0, hi = nt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (koff[mid] <= j) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ---- the exact tail (round 6): the sampled path's fallback, decided and run on the device
 //
 // Always enqueued after the bucket kernels, so omf_topk_encode never waits for the plan's verdict
@@ -1976,7 +1907,7 @@ __global__ __launch_bounds__(kThreads) void topk_exact_tail(TailArgs a) {
   if (ok) {  // gather: output j of tensor t is the t's sorted key cstart[t] + (j - koff[t])
     const int64_t K = a.koff[a.nt];
     for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < K; j += (int64_t)G * kThreads) {
-      const int t = koff_tensor(a.koff, a.nt, j);
+      const int t = koff_tensor(a.koff, 0, a.nt - 1, j);
       const uint64_t key = src[a.cstart[t] + (j - a.koff[t])];
       const uint32_t idx = (uint32_t)(key >> 39);
       const int64_t base = a.tbegin[t];
@@ -2000,415 +1931,6 @@ __global__ __launch_bounds__(kThreads) void topk_exact_tail(TailArgs a) {
     __hip_atomic_store(&a.status[5], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-
-// ---- tie census of a finished selection (omf_topk_torch_order)
-// torch's comparison sees magnitudes only, every NaN equal to every other: one key per class.
-__device__ __forceinline__ uint32_t tie_key(float v) {
-  const uint32_t u = __float_as_uint(v) & 0x7fffffffu;
-  return u > 0x7f800000u ? 0x7fc00000u : u;
-}
-constexpr uint32_t kNanKey = 0x7fc00000u;
-
-// Per tensor: how many source elements carry the tie key of its k-th selected value (the
-// selection's last, smallest entry).  MODE 0: the source is x and t' = fl32(alpha * x); MODE 1:
-// the source is the residual the encode left (t' where unselected).  One block per 16 Ki item.
-template <int MODE>
-__global__ __launch_bounds__(kThreads) void topk_tie_count(const float* __restrict__ src, float alpha,
-                                                           const Item* __restrict__ items,
-                                                           const int64_t* __restrict__ kk,
-                                                           const int64_t* __restrict__ koff,
-                                                           const float* __restrict__ values,
-                                                           uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t s_w[kWaves];
-  const Item it = items[blockIdx.x];
-  const uint32_t T = tie_key(values[koff[it.tensor] + kk[it.tensor] - 1]);
-  uint32_t c = 0;
-  for (int64_t e = it.begin + threadIdx.x; e < it.end; e += kThreads) {
-    const float v = MODE == 0 ? __fmul_rn(src[e], alpha) : src[e];
-    c += tie_key(v) == T ? 1u : 0u;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) s += s_w[w];
-    if (s) atomicAdd(&cnt[it.tensor], s);
-  }
-}
-
-// Per tensor (one block): does torch's CPU selection of the tensor possibly differ from this
-// encoder's (|t'| descending, index ascending) one?  It can only where magnitudes tie —
-//   dup:      two selected values with one key (their relative order is the heap's), or
-//   boundary: an unselected element with the k-th key (which of them are selected is the heap's),
-// and always in the introselect regime (k * 64 > n, torch leaves the partition order) unless
-// k == 1.  The residual holds t' - t' on the selected slots: +0 for a finite t', NaN otherwise,
-// which the count of the k-th key has to discount when that key is 0 or NaN (EF modes).
-__global__ __launch_bounds__(kThreads) void topk_tie_flags(const int64_t* __restrict__ kk,
-                                                           const int64_t* __restrict__ koff,
-                                                           const int64_t* __restrict__ tsize,
-                                                           const float* __restrict__ values,
-                                                           const uint32_t* __restrict__ cnt, int32_t ef,
-                                                           uint32_t* __restrict__ flags) {
-  __shared__ uint32_t s_w[3][kWaves];
-  const int t = blockIdx.x;
-  const int64_t k = kk[t], n = tsize[t];
-  const float* v = values + koff[t];
-  const uint32_t T = tie_key(v[k - 1]);
-  uint32_t dup = 0, sel_t = 0, fin = 0;
-  for (int64_t j = threadIdx.x; j < k; j += kThreads) {
-    const float a = v[j];
-    const uint32_t key = tie_key(a);
-    if (j + 1 < k && tie_key(v[j + 1]) == key) dup = 1;
-    sel_t += key == T ? 1u : 0u;
-    fin += (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u ? 1u : 0u;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    dup |= __shfl_xor(dup, o, 64);
-    sel_t += __shfl_xor(sel_t, o, 64);
-    fin += __shfl_xor(fin, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_w[0][threadIdx.x >> 6] = dup;
-    s_w[1][threadIdx.x >> 6] = sel_t;
-    s_w[2][threadIdx.x >> 6] = fin;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    dup = 0, sel_t = 0, fin = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      dup |= s_w[0][w];
-      sel_t += s_w[1][w];
-      fin += s_w[2][w];
-    }
-    int64_t unsel = (int64_t)cnt[t];
-    if (ef) {
-      if (T == 0u) unsel -= fin;
-      if (T == kNanKey) unsel -= k - (int64_t)fin;
-    } else {
-      unsel -= sel_t;
-    }
-    const bool boundary = unsel > 0;
-    flags[t] = (k * 64 > n) ? (k > 1 || boundary) : (dup || boundary);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void topk_scatter(const float* __restrict__ values,
-                                                         const int64_t* __restrict__ indices, int64_t k,
-                                                         float* __restrict__ y, int64_t n, int add) {
-  for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < k; j += (int64_t)gridDim.x * kThreads) {
-    const int64_t i = indices[j];
-    if (i < 0 || i >= n) continue;
-    y[i] = add ? __fadd_rn(y[i], values[j]) : values[j];
-  }
-}
-
-// Whole-arena decode of one client's selection (values/indices packed per tensor at
-// koff[t] = sum_{u<t} k_u, tensor-local indices): y[begin_t + idx] = v (mode 0/1) or += v (2).
-// Indices are unique within a client, so the read-modify-write needs no atomics.  koff comes from
-// the plan's decode table (a ratio's k_t, or a received message's counts; k_t may be 0).
-
-__global__ __launch_bounds__(kThreads) void topk_scatter_arena(const float* __restrict__ values,
-                                                               const int64_t* __restrict__ indices,
-                                                               const int64_t* __restrict__ sizes,
-                                                               const int64_t* __restrict__ begins,
-                                                               const int64_t* __restrict__ koff_g, int nt,
-                                                               int64_t ktot, float* __restrict__ y, int add) {
-  __shared__ int64_t koff[kArenaMaxTensors + 1];
-  for (int t = threadIdx.x; t <= nt; t += kThreads) koff[t] = koff_g[t];
-  __syncthreads();
-  for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < ktot; j += (int64_t)gridDim.x * kThreads) {
-    const int t = koff_tensor(koff, nt, j);
-    const int64_t i = indices[j];
-    if (i < 0 || i >= sizes[t]) continue;  // padding (-1) or out of range: skipped
-    float* p = y + begins[t] + i;
-    *p = add ? __fadd_rn(*p, values[j]) : values[j];
-  }
-}
-
-// Index check of a received selection, before anything is decoded: numpy's indexing of the
-// reference decoder (`dense[indices] = values`, global_grpc_compression.py:154/158) wraps an index
-// in [-n, 0) to i + n (rewritten here in place) and raises IndexError for one outside [-n, n).
-// The lowest tensor holding such an index is atomicMin'ed into *bad (one atomic per wave).
-__global__ __launch_bounds__(kThreads) void topk_check_idx(int64_t* __restrict__ indices,
-                                                           const int64_t* __restrict__ sizes,
-                                                           const int64_t* __restrict__ koff_g, int nt, int64_t ktot,
-                                                           int32_t* __restrict__ bad) {
-  __shared__ int64_t koff[kArenaMaxTensors + 1];
-  for (int t = threadIdx.x; t <= nt; t += kThreads) koff[t] = koff_g[t];
-  __syncthreads();
-  int lowest = 0x7fffffff;
-  for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < ktot; j += (int64_t)gridDim.x * kThreads) {
-    const int t = koff_tensor(koff, nt, j);
-    const int64_t i = indices[j], n = sizes[t];
-    if (i >= n || i < -n) lowest = min(lowest, t);
-    else if (i < 0) indices[j] = i + n;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lowest = min(lowest, __shfl_xor(lowest, o, 64));
-  if ((threadIdx.x & 63) == 0 && lowest != 0x7fffffff) atomicMin(bad, lowest);
-}
-
-// Repeated indices of a received selection (omf_topk_check_duplicates): the reference decodes a
-// layer as dense[indices] = values (numpy: the last value of a repeated index wins), which a
-// scatter does not reproduce.  MARK sets each (in-range, wrapped) index's bit of an arena bitmap
-// (plan-owned, all zero between calls) and flags the tensor whose bit was already set; the clear
-// pass resets the bits it touched, so the bitmap is zero again for the next call.
-template <bool MARK>
-__global__ __launch_bounds__(kThreads) void topk_dup_bits(const int64_t* __restrict__ indices,
-                                                          const int64_t* __restrict__ sizes,
-                                                          const int64_t* __restrict__ tbegin,
-                                                          const int64_t* __restrict__ koff_g, int nt, int64_t ktot,
-                                                          uint32_t* __restrict__ bits, int32_t* __restrict__ flags) {
-  __shared__ int64_t koff[kArenaMaxTensors + 1];
-  for (int t = threadIdx.x; t <= nt; t += kThreads) koff[t] = koff_g[t];
-  __syncthreads();
-  for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < ktot; j += (int64_t)gridDim.x * kThreads) {
-    const int t = koff_tensor(koff, nt, j);
-    const int64_t i = indices[j];
-    if (i < 0 || i >= sizes[t]) continue;  // out of range: omf_topk_check_indices reports it
-    const uint64_t pos = (uint64_t)(tbegin[t] + i);
-    const uint32_t b = 1u << (pos & 31);
-    if (MARK) {
-      if (atomicOr(&bits[pos >> 5], b) & b) flags[t] = 1;
-    } else {
-      atomicAnd(&bits[pos >> 5], ~b);
-    }
-  }
-}
-
-// ---------------------------------------------------------------- tiled zero-fill decode (mode 0)
-// y := 0 over the whole arena, then y[begin_t + idx] = v for one client's selection, as ONE
-// streaming write of the arena: the scattered 4-byte stores of a fill-then-scatter decode reach
-// HBM as partial-line read-modify-writes (3.7x their bytes, profiles/r02).  So the values are
-// first placed into per-super-tile buckets (64 Ki arena elements each; a bucket's capacity is
-// twice the selection's expected count there + 256, fixed per (plan, ratio); what does not fit
-// goes to an overflow list), then one workgroup per super-tile stages its bucket in LDS, builds
-// each 16 Ki-element sub-tile in LDS (zeros + its values) and streams it out with 16-byte
-// non-temporal stores; a last kernel applies the (normally empty) overflow list.
-#ifndef OMF_DEC_SUB_BITS  // experiment builds may override it (scripts/exp/tk_dec_ab.sh)
-#define OMF_DEC_SUB_BITS 14
-#endif
-constexpr int kDecSubBits = OMF_DEC_SUB_BITS;
-constexpr int kDecSubs = 1 << (kDecSuperBits - kDecSubBits);
-#ifndef OMF_DEC_TILE_THREADS  // experiment builds may override it (scripts/exp/tk_dec_ab.sh)
-#define OMF_DEC_TILE_THREADS 512
-#endif
-constexpr int kDecTileThreads = OMF_DEC_TILE_THREADS;
-#ifndef OMF_DEC_STAGE
-#define OMF_DEC_STAGE 2048
-#endif
-#ifndef OMF_DEC_MASK  // experiment builds may override it (scripts/exp/tk_dec_ab.sh)
-#define OMF_DEC_MASK 0
-#endif
-constexpr int kDecStage = OMF_DEC_STAGE;  // bucket entries a tile workgroup stages in LDS (more: read from L2)
-
-__device__ __forceinline__ int dec_tensor_of(const int64_t* __restrict__ koff, int lo, int hi, int64_t j) {
-  while (lo < hi) {  // koff[t] <= j < koff[t + 1]
-    const int mid = (lo + hi + 1) >> 1;
-    if (koff[mid] <= j) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// Place one block of kDecChunk consecutive selected values into their super-tiles' buckets:
-// LDS counts over the block's super-tile range, one global reservation per touched super-tile,
-// then (position in the super-tile << 32 | value bits) at its slot, or into the overflow list
-// (arena position << 32 | value bits) past the bucket's capacity.  The block's first and last
-// tensor come from the plan's per-ratio table (blk_t); a block that spans several tensors (the
-// small ones) finds each value's tensor by a binary search of their koff staged in LDS.
-constexpr int kDecWin = 512;
-__global__ __launch_bounds__(kThreads) void topk_dec_place(const float* __restrict__ values,
-                                                           const int64_t* __restrict__ indices,
-                                                           const int64_t* __restrict__ sizes,
-                                                           const int64_t* __restrict__ begins,
-                                                           const int64_t* __restrict__ koff,
-                                                           const uint32_t* __restrict__ blk_t, int64_t ktot,
-                                                           const uint32_t* __restrict__ cap_base,
-                                                           uint32_t* __restrict__ fill, uint64_t* __restrict__ pairs,
-                                                           uint32_t* __restrict__ ovf_cnt, uint64_t* __restrict__ ovf) {
-  extern __shared__ uint32_t h[];  // the block's super-tile range (dynamic, <= kDecMaxSuper)
-  __shared__ int64_t s_koff[kDecWin + 1];
-  const int64_t j0 = (int64_t)blockIdx.x * kDecChunk, j1 = min(j0 + kDecChunk, ktot);
-  const int tf = (int)blk_t[2 * blockIdx.x], tl = (int)blk_t[2 * blockIdx.x + 1];
-  const bool win = tl - tf < kDecWin;
-  if (tf != tl && win)
-    for (int i = threadIdx.x; i <= tl - tf; i += kThreads) s_koff[i] = koff[tf + i];
-  const uint32_t s_lo = (uint32_t)(begins[tf] >> kDecSuperBits);
-  const uint32_t nbin = (uint32_t)((begins[tl] + sizes[tl] - 1) >> kDecSuperBits) - s_lo + 1;
-  for (uint32_t b = threadIdx.x; b < nbin; b += kThreads) h[b] = 0;
-  constexpr int U = kDecChunk / kThreads;
-  int64_t pos[U];
-  float val[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {  // every load issued before any is used
-    const int64_t j = min(j0 + threadIdx.x + (int64_t)u * kThreads, j1 - 1);
-    pos[u] = indices[j];
-    val[u] = values[j];
-  }
-  __syncthreads();  // h zeroed
-  uint32_t rank[U];
-  if (tf == tl) {
-    const int64_t n = sizes[tf], b0 = begins[tf];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t j = j0 + threadIdx.x + (int64_t)u * kThreads;
-      const int64_t i = pos[u];
-      pos[u] = (j >= j1 || i < 0 || i >= n) ? -1 : b0 + i;  // padding / out of range: skipped
-      rank[u] = pos[u] >= 0 ? atomicAdd(&h[(uint32_t)(pos[u] >> kDecSuperBits) - s_lo], 1u) : 0u;
-    }
-  } else {
-    int tt[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t j = min(j0 + threadIdx.x + (int64_t)u * kThreads, j1 - 1);
-      if (win) {  // koff[t] <= j < koff[t + 1], in LDS
-        int lo = 0, hi = tl - tf;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (s_koff[mid] <= j) lo = mid;
-          else hi = mid - 1;
-        }
-        tt[u] = tf + lo;
-      } else {
-        tt[u] = dec_tensor_of(koff, tf, tl, j);
-      }
-    }
-    int64_t n[U], b0[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      n[u] = sizes[tt[u]];
-      b0[u] = begins[tt[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t j = j0 + threadIdx.x + (int64_t)u * kThreads;
-      const int64_t i = pos[u];
-      pos[u] = (j >= j1 || i < 0 || i >= n[u]) ? -1 : b0[u] + i;  // padding / out of range: skipped
-      rank[u] = pos[u] >= 0 ? atomicAdd(&h[(uint32_t)(pos[u] >> kDecSuperBits) - s_lo], 1u) : 0u;
-    }
-  }
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < nbin; b += kThreads)
-    if (h[b]) h[b] = atomicAdd(&fill[s_lo + b], h[b]);  // this block's first slot in the bucket
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if (pos[u] < 0) continue;
-    const uint32_t s = (uint32_t)(pos[u] >> kDecSuperBits);
-    const uint32_t slot = h[s - s_lo] + rank[u], base = cap_base[s], cap = cap_base[s + 1] - base;
-    const uint64_t vb = (uint64_t)__float_as_uint(val[u]);
-    if (slot < cap) {
-      pairs[(uint64_t)base + slot] = ((uint64_t)(pos[u] & ((1 << kDecSuperBits) - 1)) << 32) | vb;
-    } else {  // bucket full (a selection far denser here than expected): the overflow list
-      ovf[atomicAdd(ovf_cnt, 1u)] = ((uint64_t)pos[u] << 32) | vb;
-    }
-  }
-}
-
-// One workgroup per super-tile: its bucket staged in LDS (up to kDecStage entries; a larger
-// one is read from L2 per sub-tile), then per 16 Ki-element sub-tile: zeros in LDS, its values,
-// 16-byte non-temporal stores (the arena's partial last sub-tile element by element).
-__global__ __launch_bounds__(kDecTileThreads) void topk_dec_tiles(const uint64_t* __restrict__ pairs,
-                                                                  const uint32_t* __restrict__ cap_base,
-                                                                  uint32_t* __restrict__ fill,
-                                                                  float* __restrict__ y, int64_t arena_end) {
-  __shared__ float4 tile[(1 << kDecSubBits) / 4];
-  __shared__ uint64_t stage[kDecStage];
-  __shared__ uint32_t s_fill;
-#if OMF_DEC_MASK
-  __shared__ uint32_t s_mask[(1 << kDecSubBits) / 32];  // which tile elements this sub-tile set
-#endif
-  float* tf = reinterpret_cast<float*>(tile);
-  const uint32_t s = blockIdx.x;
-  const uint32_t base = cap_base[s];
-  if (threadIdx.x == 0) {  // read the bucket's count and leave it zero for the next call
-    s_fill = fill[s];
-    fill[s] = 0u;
-  }
-  __syncthreads();
-  const uint32_t cnt = min(s_fill, cap_base[s + 1] - base);
-  const bool staged = cnt <= (uint32_t)kDecStage;
-  const uint64_t* src = staged ? stage : pairs + base;
-  if (staged)
-    for (uint32_t p = threadIdx.x; p < cnt; p += kDecTileThreads) stage[p] = pairs[base + p];
-  constexpr int Q = (1 << kDecSubBits) / 4 / kDecTileThreads;  // float4 per thread per sub-tile
-  for (int sub = 0; sub < kDecSubs; ++sub) {
-    const int64_t b0 = ((int64_t)s << kDecSuperBits) + ((int64_t)sub << kDecSubBits);
-    if (b0 >= arena_end) break;  // block-uniform
-#if OMF_DEC_MASK
-    // a bit per element instead of a zeroed tile: 2 KiB of LDS writes per sub-tile, not 64
-    for (int i = threadIdx.x; i < (1 << kDecSubBits) / 32; i += kDecTileThreads) s_mask[i] = 0u;
-    __syncthreads();  // (also: the staged bucket is complete)
-    for (uint32_t p = threadIdx.x; p < cnt; p += kDecTileThreads) {
-      const uint64_t pr = src[p];
-      const uint32_t in = (uint32_t)(pr >> 32);
-      if ((int)(in >> kDecSubBits) == sub) {
-        const uint32_t l = in & ((1u << kDecSubBits) - 1);
-        tf[l] = __uint_as_float((uint32_t)pr);
-        atomicOr(&s_mask[l >> 5], 1u << (l & 31));
-      }
-    }
-    __syncthreads();
-    if (b0 + (1 << kDecSubBits) <= arena_end) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const int e = 4 * (threadIdx.x + q * kDecTileThreads);
-        const uint32_t m = (s_mask[e >> 5] >> (e & 31)) & 0xfu;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (m) {  // elements of this sub-tile's earlier contents are stale: take the set ones only
-          const float4 t = tile[threadIdx.x + q * kDecTileThreads];
-          o.x = (m & 1u) ? t.x : 0.f; o.y = (m & 2u) ? t.y : 0.f;
-          o.z = (m & 4u) ? t.z : 0.f; o.w = (m & 8u) ? t.w : 0.f;
-        }
-        store_nt(y + b0 + e, o);
-      }
-    } else {
-      for (int64_t e = threadIdx.x; b0 + e < arena_end; e += kDecTileThreads)
-        y[b0 + e] = ((s_mask[e >> 5] >> (e & 31)) & 1u) ? tf[e] : 0.f;
-    }
-    __syncthreads();
-#else
-#pragma unroll
-    for (int q = 0; q < Q; ++q) tile[threadIdx.x + q * kDecTileThreads] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();  // (also: the staged bucket is complete)
-    for (uint32_t p = threadIdx.x; p < cnt; p += kDecTileThreads) {
-      const uint64_t pr = src[p];
-      const uint32_t in = (uint32_t)(pr >> 32);
-      if ((int)(in >> kDecSubBits) == sub) tf[in & ((1u << kDecSubBits) - 1)] = __uint_as_float((uint32_t)pr);
-    }
-    __syncthreads();
-    if (b0 + (1 << kDecSubBits) <= arena_end) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const int e = 4 * (threadIdx.x + q * kDecTileThreads);
-        store_nt(y + b0 + e, tile[threadIdx.x + q * kDecTileThreads]);
-      }
-    } else {
-      for (int64_t e = threadIdx.x; b0 + e < arena_end; e += kDecTileThreads) y[b0 + e] = tf[e];
-    }
-    __syncthreads();
-#endif
-  }
-}
-
-// The overflow list after the tiles (normally empty; one block), its count left zero for the next call.
-__global__ __launch_bounds__(kThreads) void topk_dec_overflow(uint32_t* __restrict__ ovf_cnt,
-                                                              const uint64_t* __restrict__ ovf, float* __restrict__ y) {
-  const uint32_t n = *ovf_cnt;
-  for (uint32_t j = threadIdx.x; j < n; j += kThreads) {
-    const uint64_t pr = ovf[j];
-    y[pr >> 32] = __uint_as_float((uint32_t)pr);
-  }
-  __syncthreads();  // every thread has read the count
-  if (threadIdx.x == 0 && n) *ovf_cnt = 0u;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------- host side
@@ -2462,7 +1984,7 @@ int pipe_streams(HostSync* h) {
 // per-tensor plans, the bucket sorts) run beside the next group's streaming pass instead of after the
 // whole arena's.
 int topk_group_count(const omf_plan* p, const TopkKnobs& kn) {
-  // Off by default: measured on Llama-400M (scripts/exp/tk_env_ab.py) more groups only add time —
+  // Off by default: measured on Llama-400M more groups only add time —
   // 1.089 ms with one group, 1.156 / 1.192 / 1.266 ms with 2 / 3 / 4 (the latency-bound kernels
   // do not shrink with their group, and their random stores slow the streaming pass beside them).
   int g = kn.groups;
@@ -2606,6 +2128,19 @@ int setup_table(omf_plan* p, double ratio, int64_t max_runs, hipStream_t st, uin
 
 }  // namespace
 
+int omf::topk_encode_tables(omf_plan* plan, double ratio, void* ws, size_t ws_bytes, hipStream_t st, EncodeWs* w,
+                            SetupTable* tb) {  // omf_topk_enc.h
+  const EncodeWsLayout& L = encode_ws(plan);
+  if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
+  DeviceGuard g(plan->device);
+  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
+  *w = L.carve.bind(ws);
+  const EncodeSetup* es = nullptr;
+  if (int r = setup_table(plan, ratio, sample_max_runs(knobs(plan)), st, w->status, &es)) return r;
+  *tb = es->dev;
+  return OMF_OK;
+}
+
 extern "C" {
 
 int64_t omf_topk_k(int64_t numel, double ratio) { return topk_k(numel, ratio); }
@@ -2715,18 +2250,11 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
       // words) is the fork point of the second stream
       hipStream_t s = (gi & 1) ? hsync->side : st;
       const dim3 sblk(1024);
-      if (G.nsb) {
-        if (residual_mode == 1)
-          hipLaunchKernelGGL((topk_sample<1>), dim3(G.nsb), sblk, 0, s, x, residual, alpha, d_begins, d_sizes,
-                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, w.status, tb.kk, tb.tfirst,
-                             tb.tlast, w.tkey, w.hist, w.item_cnt, w.thi, w.fmap, w.tlo, w.fcount, w.fhist, G.sb0,
-                             sure_zc);
-        else
-          hipLaunchKernelGGL((topk_sample<0>), dim3(G.nsb), sblk, 0, s, x, residual, alpha, d_begins, d_sizes,
-                             (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive, w.status, tb.kk, tb.tfirst,
-                             tb.tlast, w.tkey, w.hist, w.item_cnt, w.thi, w.fmap, w.tlo, w.fcount, w.fhist, G.sb0,
-                             sure_zc);
-      }
+      if (G.nsb)
+        hipLaunchKernelGGL(residual_mode == 1 ? topk_sample<1> : topk_sample<0>, dim3(G.nsb), sblk, 0, s, x, residual,
+                           alpha, d_begins, d_sizes, (const uint32_t*)tb.smap, max_runs, tb.gh, tb.gz, tb.arrive,
+                           w.status, tb.kk, tb.tfirst, tb.tlast, w.tkey, w.hist, w.item_cnt, w.thi, w.fmap, w.tlo,
+                           w.fcount, w.fhist, G.sb0, sure_zc);
       if (gi == 0 && groups.size() > 1) {
         OMF_HIP(hipEventRecord(hsync->fork, st));
         OMF_HIP(hipStreamWaitEvent(hsync->side, hsync->fork, 0));
@@ -2736,15 +2264,9 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
       // runs beside g's streaming pass rather than two passes sharing the memory system.
       if (gi > 0) OMF_HIP(hipStreamWaitEvent(s, hsync->fused[(gi - 1) & 1], 0));
       const dim3 fgrid(G.nsub);
-      if (residual_mode == 1)
-        hipLaunchKernelGGL((topk_fused<1>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
-                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
-      else if (residual_mode == 2)
-        hipLaunchKernelGGL((topk_fused<2>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
-                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
-      else
-        hipLaunchKernelGGL((topk_fused<0>), fgrid, dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins,
-                           w.tkey, w.thi, w.sub_cnt, w.item_cnt, w.cand, G.sub0);
+      hipLaunchKernelGGL(residual_mode == 1 ? topk_fused<1> : residual_mode == 2 ? topk_fused<2> : topk_fused<0>, fgrid,
+                         dim3(kSubThreads), 0, s, x, residual, alpha, items, d_begins, w.tkey, w.thi, w.sub_cnt,
+                         w.item_cnt, w.cand, G.sub0);
       if (groups.size() > 1) OMF_HIP(hipEventRecord(hsync->fused[gi & 1], s));
       // fast path: exact fine-bin histograms, bucket plan
       const dim3 supgrid(G.nsup), supblk(1024);
@@ -2763,14 +2285,9 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
                            G.t0);
       if (!forced) {
         if (!(small && kn.planned_scatter)) {  // (the planned scatter has run above)
-          if (small)
-            hipLaunchKernelGGL(topk_bucket_scatter<true>, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt,
-                               (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fbucket, tb.bbase, w.bstart,
-                               w.bfill, tb.kb2, d_begins, rz, w.sorted, w.status, w.thi, G.sup0);
-          else
-            hipLaunchKernelGGL(topk_bucket_scatter<false>, supgrid, supblk, 0, s, w.cand, items, w.sub_cnt,
-                               (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fbucket, tb.bbase, w.bstart,
-                               w.bfill, tb.kb2, d_begins, rz, w.sorted, w.status, w.thi, G.sup0);
+          hipLaunchKernelGGL(small ? topk_bucket_scatter<true> : topk_bucket_scatter<false>, supgrid, supblk, 0, s,
+                             w.cand, items, w.sub_cnt, (const uint4*)tb.supinfo, w.fmap, w.tlo, w.fcount, w.fbucket,
+                             tb.bbase, w.bstart, w.bfill, tb.kb2, d_begins, rz, w.sorted, w.status, w.thi, G.sup0);
         }
         hipLaunchKernelGGL(topk_bucket_sort, dim3(G.nbk), dim3(kBT), 0, s, w.sorted, w.brec, tb.kk, tb.koff, d_begins,
                            d_sizes, rz, values, indices, w.status, w.fmap, w.tlo, w.fcount, w.fhist, w.fse, w.thi, dbg,
@@ -2824,12 +2341,9 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
     return OMF_OK;
   } else {
     ++stats.exact;
-    if (residual_mode == 0)
-      hipLaunchKernelGGL((topk_prep_hist<0>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
-    else if (residual_mode == 1)
-      hipLaunchKernelGGL((topk_prep_hist<1>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
-    else
-      hipLaunchKernelGGL((topk_prep_hist<2>), grid, blk, 0, st, x, residual, alpha, items, w.hist);
+    hipLaunchKernelGGL(
+        residual_mode == 0 ? topk_prep_hist<0> : residual_mode == 1 ? topk_prep_hist<1> : topk_prep_hist<2>, grid, blk,
+        0, st, x, residual, alpha, items, w.hist);
     hipLaunchKernelGGL(topk_select_bin, dim3((unsigned)nt), blk, 0, st, w.hist, tb.kk, w.bin);
     hipLaunchKernelGGL(topk_collect, grid, blk, 0, st, tp, scale, items, d_begins, w.bin, w.cnt, w.cand);
     hipLaunchKernelGGL(topk_segments, dim3(((unsigned)nt + kThreads - 1) / kThreads), blk, 0, st, nt, d_begins, w.cnt,
@@ -2843,499 +2357,6 @@ int omf_topk_encode(omf_plan* plan, const float* x, float* residual, int32_t res
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((kmax + kThreads - 1) / kThreads, 1024));
   hipLaunchKernelGGL(topk_gather, dim3(gx, (unsigned)nt), blk, 0, st, tp, scale, rz, w.sorted, d_begins, d_sizes,
                      tb.kk, tb.koff, values, indices);
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
-}  // extern "C"
-
-namespace omf {
-int torch_topk_select(const float* t, int64_t n, int64_t k, int64_t* out);  // omf_topk_host.cpp
-}
-
-namespace {
-
-// One tensor of omf_topk_torch_order: its t' fetched (the residual with the selected values put
-// back, or fl32(alpha * x)), torch's CPU selection recomputed on the host, and the tensor's values /
-// indices (and, when the selected set changed, its residual) written back.  Returns OMF_OK or an
-// error with *msg set (the worker's thread-local error string is not the caller's).
-#ifdef OMF_EXP_TIE_TS
-std::atomic<int64_t> g_tie_us[3];  // summed over the call's tensors: fetch, select, write-back
-#endif
-// Host buffers for t', kept from one omf_topk_torch_order call to the next (a fresh 128 MB array per
-// 32 Mi-element tensor cost its zero fill and page faults on every call).  A tensor takes the smallest
-// kept buffer that holds it, else a new one; at most kTieKeepBytes stay kept (a released buffer beyond
-// that is freed).  Never zero-filled: the copy writes every element.
-constexpr size_t kTieKeepBytes = (size_t)768 << 20;
-struct TieBuf {
-  std::unique_ptr<float[]> p;
-  size_t cap = 0;
-};
-std::mutex g_tie_mu;
-std::vector<TieBuf> g_tie_pool;
-size_t g_tie_kept = 0;
-TieBuf tie_acquire(size_t n) {
-  TieBuf b;
-  {
-    std::lock_guard<std::mutex> lk(g_tie_mu);
-    int best = -1;  // the smallest kept buffer of >= n floats
-    for (int i = 0; i < (int)g_tie_pool.size(); ++i)
-      if (g_tie_pool[i].cap >= n && (best < 0 || g_tie_pool[i].cap < g_tie_pool[best].cap)) best = i;
-    if (best >= 0) {
-      b = std::move(g_tie_pool[best]);
-      g_tie_pool.erase(g_tie_pool.begin() + best);
-      g_tie_kept -= 4 * b.cap;
-    }
-  }
-  if (!b.p) {  // none kept holds it: a new one (the kept ones stay for smaller tensors)
-    b.p.reset(new (std::nothrow) float[std::max<size_t>(n, 1)]);
-    b.cap = b.p ? std::max<size_t>(n, 1) : 0;
-  }
-  return b;
-}
-void tie_release(TieBuf&& b) {
-  if (!b.p) return;
-  std::lock_guard<std::mutex> lk(g_tie_mu);
-  if (g_tie_kept + 4 * b.cap > kTieKeepBytes) return;  // freed
-  g_tie_kept += 4 * b.cap;
-  g_tie_pool.push_back(std::move(b));
-}
-struct TieLease {
-  TieBuf b;
-  explicit TieLease(size_t n) : b(tie_acquire(n)) {}
-  ~TieLease() { tie_release(std::move(b)); }
-  float* data() { return b.p.get(); }
-  float& operator[](size_t i) { return b.p[i]; }
-};
-int reorder_tensor(hipStream_t s, const float* src, float* residual, bool ef, float alpha, int64_t off, int64_t n,
-                   int64_t k, float* values, int64_t* indices, bool* changed, std::string* msg) {
-#ifdef OMF_EXP_TIE_TS  // experiment builds: phase times of the rewrites (allocation counted as fetch)
-  const auto ts0 = std::chrono::steady_clock::now();
-#endif
-  TieLease tp((size_t)n);
-  std::vector<float> v, nv;
-  std::vector<int64_t> ix, sel;
-  try {
-    if (!tp.data()) throw std::bad_alloc();
-    v.resize((size_t)k);
-    nv.resize((size_t)k);
-    ix.resize((size_t)k);
-    sel.resize((size_t)k);
-  } catch (const std::bad_alloc&) {
-    *msg = "omf_topk_torch_order: host buffers";
-    return OMF_ENOMEM;
-  }
-  auto hip = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess) *msg = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipSuccess;
-  };
-  if (!hip(hipMemcpyAsync(tp.data(), src + off, 4 * (size_t)n, hipMemcpyDeviceToHost, s), "t' to host") ||
-      !hip(hipMemcpyAsync(v.data(), values, 4 * (size_t)k, hipMemcpyDeviceToHost, s), "values to host") ||
-      !hip(hipMemcpyAsync(ix.data(), indices, 8 * (size_t)k, hipMemcpyDeviceToHost, s), "indices to host") ||
-      !hip(hipStreamSynchronize(s), "copy to host"))
-    return OMF_EHIP;
-#ifdef OMF_EXP_TIE_TS
-  const auto ts1 = std::chrono::steady_clock::now();
-#endif
-  if (ef) {
-    for (int64_t j = 0; j < k; ++j)
-      if (ix[j] >= 0 && ix[j] < n) tp[ix[j]] = v[j];
-  } else if (alpha != 1.0f) {
-    for (int64_t i = 0; i < n; ++i) tp[i] = tp[i] * alpha;  // one IEEE multiply, as the encoder's
-  }
-  if (int rc = omf::torch_topk_select(tp.data(), n, k, sel.data())) {
-    *msg = omf_last_error();
-    return rc;
-  }
-#ifdef OMF_EXP_TIE_TS
-  const auto ts2 = std::chrono::steady_clock::now();
-  struct Report {
-    int64_t n;
-    std::chrono::steady_clock::time_point a, b, c;
-    ~Report() {
-      const auto d = std::chrono::steady_clock::now();
-      g_tie_us[0] += std::chrono::duration_cast<std::chrono::microseconds>(b - a).count();
-      g_tie_us[1] += std::chrono::duration_cast<std::chrono::microseconds>(c - b).count();
-      g_tie_us[2] += std::chrono::duration_cast<std::chrono::microseconds>(d - c).count();
-      if (n >= (1 << 24))
-        fprintf(stderr, "TIE_TS n=%lld fetch=%.1f select=%.1f writeback=%.1f ms\n", (long long)n,
-                std::chrono::duration<double, std::milli>(b - a).count(),
-                std::chrono::duration<double, std::milli>(c - b).count(),
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c).count());
-    }
-  } report{n, ts0, ts1, ts2};
-#endif
-  if (sel == ix) return OMF_OK;
-  *changed = true;
-  for (int64_t j = 0; j < k; ++j) nv[j] = tp[sel[j]];
-  bool same_set = true;
-  if (ef) {
-    // Both selections are exact top-k multisets of the magnitude keys (every NaN one key), so they
-    // can differ only among the elements whose key is the smallest selected one, T: compare those
-    // index sets (a handful; sorting both whole selections took 30-40 ms on a 32 Mi tensor).
-    auto key = [](float f) {
-      uint32_t u;
-      std::memcpy(&u, &f, 4);
-      u &= 0x7fffffffu;
-      return u > 0x7f800000u ? 0x7fc00000u : u;
-    };
-    uint32_t T = 0xffffffffu;
-    for (int64_t j = 0; j < k; ++j) T = std::min(T, key(v[j]));
-    std::vector<int64_t> a, b;
-    for (int64_t j = 0; j < k; ++j) {
-      if (key(v[j]) == T) a.push_back(ix[j]);
-      if (key(nv[j]) == T) b.push_back(sel[j]);
-    }
-    std::sort(a.begin(), a.end());
-    std::sort(b.begin(), b.end());
-    same_set = a == b;
-  }
-  if (!same_set) {  // the residual: t' with torch's selection zeroed (t' - t')
-    // (spelled out, not t' - t': omf_codec.h promises the device's NaN for an infinite t' whichever
-    // path wrote the slot, and the sign of inf - inf's NaN is the host platform's)
-    const float inf_nan = std::bit_cast<float>(0xffc00000u);
-    for (int64_t j = 0; j < k; ++j) {
-      float& e = tp[sel[j]];
-      e = std::isfinite(e) ? 0.0f : std::isnan(e) ? e : inf_nan;
-    }
-    if (!hip(hipMemcpyAsync(residual + off, tp.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s), "residual to device"))
-      return OMF_EHIP;
-  }
-  if (!hip(hipMemcpyAsync(values, nv.data(), 4 * (size_t)k, hipMemcpyHostToDevice, s), "values to device") ||
-      !hip(hipMemcpyAsync(indices, sel.data(), 8 * (size_t)k, hipMemcpyHostToDevice, s), "indices to device") ||
-      !hip(hipStreamSynchronize(s), "copy to device"))
-    return OMF_EHIP;
-  return OMF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int omf_topk_torch_order(omf_plan* plan, const float* x, float* residual, int32_t residual_mode, double ratio,
-                         float alpha, float* values, int64_t* indices, void* ws, size_t ws_bytes, void* stream,
-                         int64_t* n_reordered) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  if (!values || !indices || !ws) return fail(OMF_EINVAL, "values, indices and ws must be non-NULL");
-  if (residual_mode < 0 || residual_mode > 2 || (residual_mode != 0 && !residual) || (residual_mode == 0 && !x))
-    return fail(OMF_EINVAL, "residual_mode 0 needs x, modes 1 / 2 the residual the encode updated");
-  if (!(ratio == ratio)) return fail(OMF_EINVAL, "ratio is NaN");
-  const std::vector<int64_t>& sizes = plan->sizes;
-  const std::vector<int64_t>& offsets = plan->offsets;
-  const int32_t nt = (int32_t)sizes.size();
-  std::vector<int64_t> K(nt + 1, 0);
-  for (int32_t t = 0; t < nt; ++t) {
-    const int64_t k = omf_topk_k(sizes[t], ratio);
-    if (k > sizes[t]) return fail(OMF_EINVAL, "selected index k out of range (k > numel): compress_ratio too large");
-    K[t + 1] = K[t] + k;
-  }
-  const EncodeWsLayout& L = encode_ws(plan);
-  if (ws_bytes < L.total) return fail(OMF_EINVAL, "workspace too small (see omf_topk_workspace_bytes)");
-  if (n_reordered) *n_reordered = 0;
-  if (nt == 0) return OMF_OK;
-  const int dev = plan->device;
-  DeviceGuard g(dev);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;
-  const EncodeWs w = L.carve.bind(ws);
-  uint32_t *cnt = w.cnt, *flags = w.flag;  // the encode's scratch, free once it is done
-  const EncodeSetup* es = nullptr;
-  if (int r = setup_table(plan, ratio, sample_max_runs(knobs(plan)), st, w.status, &es)) return r;
-  const SetupTable& tb = es->dev;
-  const int64_t n_items = plan->n_flat;
-  const Item* items = plan->d_flat;
-  const bool ef = residual_mode != 0;
-  OMF_HIP(hipMemsetAsync(cnt, 0, 4 * (size_t)nt, st));
-  if (n_items > 0) {
-    if (ef)
-      hipLaunchKernelGGL((topk_tie_count<1>), dim3((unsigned)n_items), dim3(kThreads), 0, st, residual, 1.0f, items,
-                         tb.kk, tb.koff, values, cnt);
-    else
-      hipLaunchKernelGGL((topk_tie_count<0>), dim3((unsigned)n_items), dim3(kThreads), 0, st, x, alpha, items, tb.kk,
-                         tb.koff, values, cnt);
-  }
-  hipLaunchKernelGGL(topk_tie_flags, dim3((unsigned)nt), dim3(kThreads), 0, st, tb.kk, tb.koff,
-                     plan->d_sizes, values, cnt, ef ? 1 : 0, flags);
-  OMF_HIP(hipGetLastError());
-  std::vector<uint32_t> hflags(nt);
-  OMF_HIP(hipMemcpyAsync(hflags.data(), flags, 4 * (size_t)nt, hipMemcpyDeviceToHost, st));
-  OMF_HIP(hipStreamSynchronize(st));
-  std::vector<int32_t> todo;
-  for (int32_t t = 0; t < nt; ++t)
-    if (hflags[t]) todo.push_back(t);
-  if (todo.empty()) return OMF_OK;
-  std::sort(todo.begin(), todo.end(), [&](int32_t a, int32_t b) { return sizes[a] > sizes[b]; });  // largest first
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const int nw = (int)std::min<size_t>(todo.size(), std::min(16u, hw));
-  std::atomic<size_t> next{0};
-  std::atomic<int64_t> changed_count{0};
-  std::mutex err_mu;
-  int err = OMF_OK;
-  std::string err_msg;
-  const float* src = ef ? residual : x;
-  auto work = [&]() {
-    DeviceGuard wg(dev);
-    hipStream_t s = nullptr;
-    if (!wg.ok || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
-      std::lock_guard<std::mutex> lk(err_mu);
-      if (!err) err = OMF_EHIP, err_msg = "omf_topk_torch_order: worker stream";
-      return;
-    }
-    for (size_t i = next++; i < todo.size(); i = next++) {
-      const int32_t t = todo[i];
-      bool changed = false;
-      std::string msg;
-      const int rc = reorder_tensor(s, src, residual, ef, alpha, offsets[t], sizes[t], K[t + 1] - K[t], values + K[t],
-                                    indices + K[t], &changed, &msg);
-      if (rc) {
-        std::lock_guard<std::mutex> lk(err_mu);
-        if (!err) err = rc, err_msg = "omf_topk_torch_order: tensor " + std::to_string(t) + ": " + msg;
-        break;
-      }
-      if (changed) ++changed_count;
-    }
-    (void)hipStreamDestroy(s);
-  };
-#ifdef OMF_EXP_TIE_TS
-  for (auto& g : g_tie_us) g = 0;
-  const auto tw0 = std::chrono::steady_clock::now();
-#endif
-  std::vector<std::thread> pool;
-  for (int i = 1; i < nw; ++i) pool.emplace_back(work);
-  work();
-  for (std::thread& th : pool) th.join();
-#ifdef OMF_EXP_TIE_TS
-  fprintf(stderr, "TIE_CALL tensors=%zu workers=%d wall=%.1f ms  sums: fetch=%.1f select=%.1f writeback=%.1f ms\n",
-          todo.size(), nw, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count(),
-          g_tie_us[0] / 1e3, g_tie_us[1] / 1e3, g_tie_us[2] / 1e3);
-#endif
-  if (err) return fail(err, err_msg);
-  if (n_reordered) *n_reordered = changed_count.load();
-  return OMF_OK;
-}
-
-// Whole-arena decode.  Plan-owned constant tables per selection layout (omf_plan.h topk_table, keyed
-// by the ratio; topk_table_counts, keyed by a received message's per-tensor counts) and the caller
-// workspace of the tiled zero-fill decode: topk_layout's DecodeTables / DecTable / DecWs.
-struct DecTables {
-  DecTable dev{};
-  int32_t nsuper = 0;
-  uint64_t cap_total = 0;
-};
-
-// k_t of every tensor at `ratio` (omf_topk_k); false when some k_t > n_t.
-static bool ratio_counts(const omf_plan* plan, double ratio, std::vector<int64_t>& ks) {
-  const std::vector<int64_t>& sizes = plan->sizes;
-  ks.resize(sizes.size());
-  for (size_t t = 0; t < sizes.size(); ++t) {
-    ks[t] = omf_topk_k(sizes[t], ratio);
-    if (ks[t] > sizes[t]) return false;
-  }
-  return true;
-}
-
-// Explicit counts: 0 <= counts[t] <= n_t (a received selection of more values than its tensor
-// has elements would need duplicates; the caller decodes such a layer on its own).
-static int check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot) {
-  if (!counts) return fail(OMF_EINVAL, "counts is NULL");
-  const std::vector<int64_t>& sizes = plan->sizes;
-  int64_t s = 0;
-  for (size_t t = 0; t < sizes.size(); ++t) {
-    if (counts[t] < 0 || counts[t] > sizes[t])
-      return fail(OMF_EINVAL, "counts[t] must be in [0, sizes[t]] (tensor " + std::to_string(t) + ")");
-    s += counts[t];
-  }
-  *ktot = s;
-  return OMF_OK;
-}
-
-static uint64_t ratio_key(double ratio) {
-  uint64_t k;
-  std::memcpy(&k, &ratio, 8);
-  return k;
-}
-
-// The plan's tables for the layout ks (computed and uploaded on first use; the bucket total is
-// kept in the table's host word).  ratio != NULL: keyed by the ratio, else by the counts.
-static int dec_tables(omf_plan* p, const int64_t* ks, int64_t ktot, const double* ratio, DecTables* out) {
-  out->nsuper = dec_nsuper(p->arena_end);
-  const Carve<DecTable> carve = dec_table_carve(p->nt, out->nsuper, dec_place_blocks(ktot));
-  bool fresh = false;
-  uint64_t* host = nullptr;
-  void* d = ratio ? topk_table(p, ratio_key(*ratio), carve.bytes(), &fresh, &host)
-                  : topk_table_counts(p, ks, carve.bytes(), &fresh, &host);
-  if (!d) return fail(OMF_ENOMEM, "Top-K decode: table allocation failed");
-  out->dev = carve.bind(d);
-  if (fresh) {
-    const DecodeTables h = dec_tables_host(p->sizes, p->offsets, p->arena_end, ks);
-    OMF_HIP(hipMemcpy(out->dev.koff, h.koff.data(), 8 * h.koff.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->dev.cap_base, h.cap_base.data(), 4 * h.cap_base.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->dev.blk_t, h.blk_t.data(), 4 * h.blk_t.size(), hipMemcpyHostToDevice));
-    *host = h.cap_base.back();
-  }
-  out->cap_total = *host;
-  return OMF_OK;
-}
-
-static size_t dec_ws_bytes(const omf_plan* plan, const int64_t* ks, int64_t ktot) {
-  const DecodeTables h = dec_tables_host(plan->sizes, plan->offsets, plan->arena_end, ks);
-  return dec_ws_layout(h.nsuper, h.cap_base.back(), ktot).bytes();
-}
-
-// One client's whole selection in the layout ks into the arena y (modes 0 / 1 / 2).
-static int decode_layout(omf_plan* plan, const int64_t* ks, int64_t ktot, const double* ratio, const float* values,
-                         const int64_t* indices, float* y, int32_t mode, void* ws, size_t ws_bytes, void* stream) {
-  if (mode < 0 || mode > 2) return fail(OMF_EINVAL, "Top-K arena decode: mode must be 0, 1 or 2");
-  if ((ktot && (!values || !indices)) || !y) return fail(OMF_EINVAL, "Top-K arena decode: NULL buffer");
-  const int32_t nt = plan->nt;
-  if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "Top-K arena decode: too many tensors (decode per tensor)");
-  DeviceGuard g(plan->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ae = plan->arena_end;
-  DecTables tb;
-  if (int r = dec_tables(plan, ks, ktot, ratio, &tb)) return r;
-  if (mode == 0 && ws && tb.nsuper <= kDecMaxSuper) {
-    // one streaming write of the arena (larger arenas: fill + scatter below)
-    const Carve<DecWs> d = dec_ws_layout(tb.nsuper, tb.cap_total, ktot);
-    if (ws_bytes < d.bytes()) return fail(OMF_EINVAL, "Top-K arena decode: workspace too small");
-    if (((uintptr_t)ws & 255) || ((uintptr_t)y & 15)) return fail(OMF_EINVAL, "Top-K arena decode: misaligned buffer");
-    const DecWs w = d.bind(ws);
-    uint32_t *fill = w.fill, *ovf_cnt = fill + tb.nsuper;
-    uint64_t *pairs = w.pairs, *ovf = w.ovf;
-    // fill[] and the overflow count start at zero (a zero-filled workspace) and every call leaves
-    // them so: topk_dec_tiles clears its bucket's count, topk_dec_overflow the overflow count (a
-    // memset here was two fill kernels, ~10 us per decode)
-    if (ktot > 0) {
-      const dim3 gb((unsigned)dec_place_blocks(ktot));
-      hipLaunchKernelGGL(topk_dec_place, gb, dim3(kThreads), 4 * (size_t)tb.nsuper, st, values, indices,
-                         plan->d_sizes, plan->d_begins, (const int64_t*)tb.dev.koff, (const uint32_t*)tb.dev.blk_t,
-                         ktot, (const uint32_t*)tb.dev.cap_base, fill, pairs, ovf_cnt, ovf);
-    }
-    hipLaunchKernelGGL(topk_dec_tiles, dim3((unsigned)tb.nsuper), dim3(kDecTileThreads), 0, st, (const uint64_t*)pairs,
-                       (const uint32_t*)tb.dev.cap_base, fill, y, ae);
-    if (ktot > 0) hipLaunchKernelGGL(topk_dec_overflow, dim3(1), dim3(kThreads), 0, st, ovf_cnt, (const uint64_t*)ovf, y);
-    OMF_HIP(hipGetLastError());
-    return OMF_OK;
-  }
-  if (mode == 0) OMF_HIP(hipMemsetAsync(y, 0, 4 * (size_t)ae, st));
-  if (ktot == 0) return OMF_OK;
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 4096));
-  hipLaunchKernelGGL(topk_scatter_arena, dim3(gx), dim3(kThreads), 0, st, values, indices,
-                     plan->d_sizes, plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt,
-                     ktot, y, mode == 2 ? 1 : 0);
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
-size_t omf_topk_decode_workspace_bytes(const omf_plan* plan, double ratio) {
-  if (!plan || !(ratio == ratio)) return 0;
-  std::vector<int64_t> ks;
-  if (!ratio_counts(plan, ratio, ks)) return 0;
-  int64_t ktot = 0;
-  for (int64_t k : ks) ktot += k;
-  return dec_ws_bytes(plan, ks.data(), ktot);
-}
-
-int omf_topk_decode_arena(omf_plan* plan, double ratio, const float* values, const int64_t* indices, float* y,
-                          int32_t mode, void* stream) {
-  return omf_topk_decode_arena_ws(plan, ratio, values, indices, y, mode, nullptr, 0, stream);
-}
-
-int omf_topk_decode_arena_ws(omf_plan* plan, double ratio, const float* values, const int64_t* indices, float* y,
-                             int32_t mode, void* ws, size_t ws_bytes, void* stream) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  if (!(ratio == ratio)) return fail(OMF_EINVAL, "ratio is NaN");
-  std::vector<int64_t> ks;
-  if (!ratio_counts(plan, ratio, ks))
-    return fail(OMF_EINVAL, "selected index k out of range (k > numel): compress_ratio too large");
-  int64_t ktot = 0;
-  for (int64_t k : ks) ktot += k;
-  return decode_layout(plan, ks.data(), ktot, &ratio, values, indices, y, mode, ws, ws_bytes, stream);
-}
-
-size_t omf_topk_decode_counts_workspace_bytes(const omf_plan* plan, const int64_t* counts) {
-  if (!plan || !counts) return 0;
-  int64_t ktot = 0;
-  if (check_counts(plan, counts, &ktot)) return 0;
-  return dec_ws_bytes(plan, counts, ktot);
-}
-
-int omf_topk_decode_counts(omf_plan* plan, const int64_t* counts, const float* values, const int64_t* indices, float* y,
-                           int32_t mode, void* ws, size_t ws_bytes, void* stream) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
-  return decode_layout(plan, counts, ktot, nullptr, values, indices, y, mode, ws, ws_bytes, stream);
-}
-
-int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indices, int32_t* bad, void* stream) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  if (!bad) return fail(OMF_EINVAL, "omf_topk_check_indices: bad is NULL");
-  int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
-  if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_indices: indices is NULL");
-  const int32_t nt = plan->nt;
-  if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_indices: too many tensors");
-  DeviceGuard g(plan->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;
-  DecTables tb;
-  if (int r = dec_tables(plan, counts, ktot, nullptr, &tb)) return r;
-  OMF_HIP(hipMemsetAsync(bad, 0x7f, 4, st));  // 0x7f7f7f7f: no tensor
-  if (ktot == 0) return OMF_OK;
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + 4 * kThreads - 1) / (4 * kThreads), 2048));
-  hipLaunchKernelGGL(topk_check_idx, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     (const int64_t*)tb.dev.koff, (int)nt, ktot, bad);
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
-int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64_t* indices, int32_t* flags,
-                              void* stream) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  if (!flags) return fail(OMF_EINVAL, "omf_topk_check_duplicates: flags is NULL");
-  int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
-  if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_duplicates: indices is NULL");
-  const int32_t nt = plan->nt;
-  if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_duplicates: too many tensors");
-  DeviceGuard g(plan->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;
-  OMF_HIP(hipMemsetAsync(flags, 0, 4 * (size_t)nt, st));
-  if (ktot == 0) return OMF_OK;
-  DecTables tb;
-  if (int r = dec_tables(plan, counts, ktot, nullptr, &tb)) return r;
-  // the bitmap is the plan's: a call on another stream than the plan's previous stateful launch
-  // is ordered after it (include/omf_codec.h), so two checks never mark and clear it at once
-  if (int r = plan_enter(plan, st)) return r;
-  constexpr uint64_t kDupTag = 0xD0B1E5B17A9E0000ull;
-  const size_t words = (size_t)((plan->arena_end + 31) / 32);
-  bool fresh = false;
-  uint64_t* host = nullptr;
-  uint32_t* bits = static_cast<uint32_t*>(topk_table(plan, kDupTag, 4 * words, &fresh, &host));
-  if (!bits) return fail(OMF_ENOMEM, "omf_topk_check_duplicates: bitmap allocation failed");
-  if (fresh) OMF_HIP(hipMemsetAsync(bits, 0, 4 * words, st));
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ktot + kThreads - 1) / kThreads, 2048));
-  hipLaunchKernelGGL(topk_dup_bits<true>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt, ktot, bits, flags);
-  hipLaunchKernelGGL(topk_dup_bits<false>, dim3(gx), dim3(kThreads), 0, st, indices, plan->d_sizes,
-                     plan->d_begins, (const int64_t*)tb.dev.koff, (int)nt, ktot, bits, flags);
-  OMF_HIP(hipGetLastError());
-  return plan_leave(plan, st);
-}
-
-int omf_topk_decode(const float* values, const int64_t* indices, int64_t k, float* y, int64_t n, int32_t mode,
-                    void* stream) {
-  if (k < 0 || n < 0 || mode < 0 || mode > 2) return fail(OMF_EINVAL, "omf_topk_decode: bad arguments");
-  if (n > 0 && !y) return fail(OMF_EINVAL, "omf_topk_decode: y is NULL");
-  if (k > 0 && (!values || !indices)) return fail(OMF_EINVAL, "omf_topk_decode: values/indices NULL");
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == 0 && n > 0) OMF_HIP(hipMemsetAsync(y, 0, (size_t)n * 4, st));
-  if (k == 0) return OMF_OK;
-  const unsigned g = (unsigned)std::min<int64_t>((k + kThreads - 1) / kThreads, 4096);
-  hipLaunchKernelGGL(topk_scatter, dim3(g), dim3(kThreads), 0, st, values, indices, k, y, n, mode == 2 ? 1 : 0);
   OMF_HIP(hipGetLastError());
   return OMF_OK;
 }

@@ -4,8 +4,9 @@
 // decode workspaces and of the plan-owned device tables, and the decoder's tables.
 //
 // Pure integer code: no HIP header, so tests/host/topk_layout_check.cpp runs it on a CPU under
-// sanitizers.  omf_topk.hip uploads what the builders return, binds its pointers with the carves
-// declared here and calls the same rule functions from its kernels.
+// sanitizers.  omf_topk.hip (the encoder) and omf_topk_recv.hip (decode and checks) upload what the
+// builders return, bind their pointers with the carves declared here and call the same rule functions
+// from their kernels.
 #pragma once
 
 #include <algorithm>

@@ -39,7 +39,7 @@ import numpy as np
 
 import topk_matrix_inputs as TM
 
-SUPER_BITS, SUB_BITS = 16, 14  # omf_topk_layout.h kDecSuperBits, omf_topk.hip kDecSubBits
+SUPER_BITS, SUB_BITS = 16, 14  # omf_topk_layout.h kDecSuperBits, omf_topk_recv.hip kDecSubBits
 SUPER, SUB = 1 << SUPER_BITS, 1 << SUB_BITS
 DEC_STAGE = 2048   # bucket entries a tile workgroup stages in LDS (more: read unstaged)
 DEC_CHUNK = 4096   # selected values per place block
