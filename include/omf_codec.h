@@ -64,7 +64,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 113
+#define OMF_ABI_VERSION 114
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -278,6 +278,29 @@ int32_t omf_qsgd_packed_bits(int32_t levels);
 int omf_qsgd_pack(omf_plan* plan, const void* q, int32_t width, int32_t levels, uint32_t* packed, void* stream);
 int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t levels, const float* norm, float* y,
                            int32_t accumulate, void* stream);
+
+/*
+ * omf_qsgd_decode_sum for the packed wire: K clients' packed arenas (each as omf_qsgd_pack writes
+ * it) decoded, summed in array order and divided in ONE pass that reads each packed payload once
+ * and writes y_out once.  Per element i of tensor t, with q[k]_i = code - L of client k:
+ *   s_0 = init ? y_out_i : +0
+ *   s_k = fl32(s_{k-1} + fl32(fl32(norm[k-1][t] * q[k-1]_i) / fl32(levels)))   k = 1..nclients, in array order
+ *   y_out_i = divisor != 0 ? fl32(s_K / divisor) : s_K
+ * byte for byte what omf_qsgd_decode_sum leaves for the same levels unpacked, padding included:
+ * init == 0 never reads y_out and writes every padding element of [0, arena_end)
+ * (fl32(+0 / divisor), or +0 without a divisor); init != 0 starts from y_out and leaves padding
+ * alone.  packed / norm: HOST arrays of nclients DEVICE pointers, read at the call (kernel
+ * arguments: nothing is uploaded, the call may be captured into a HIP graph); norm[k] ntensors
+ * fp32 (0 for a tensor absent from that client's message; its codes may be anything).  At most 8
+ * clients go into one launch (4 for codes wider than 10 bits), more are chained (same bytes).
+ * OMF_EINVAL, with nothing launched: nclients < 1, a NULL entry, levels outside
+ * omf_qsgd_decode_packed's range, y_out not 16-byte or a packed arena not 4-byte aligned, a plan
+ * whose offsets are not multiples of 32, y_out overlapping a packed arena
+ * (ceil(arena_end / 32) * b words) or a norm buffer.
+ */
+int omf_qsgd_decode_sum_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* norm,
+                               int32_t nclients, int32_t levels, float* y_out, int32_t init, float divisor,
+                               void* stream);
 
 /*
  * Top-K sparsification with error feedback, all tensors of the plan in one call.

@@ -67,6 +67,8 @@ SIGNATURES = {
     "omf_qsgd_packed_bits": (_c_i32, [_c_i32]),
     "omf_qsgd_pack": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "omf_qsgd_decode_packed": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p]),
+    "omf_qsgd_decode_sum_packed": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32,
+                                                  _c_p, _c_i32, _c_f32, _c_p]),
     "omf_topk_k": (_c_i64, [_c_i64, _c_f64]),
     "omf_plan_set_topk": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i64, _c_f32, _c_f32]),
     "omf_topk_stats": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_i32]),
@@ -94,7 +96,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 113 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 114 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

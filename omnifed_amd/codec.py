@@ -515,6 +515,39 @@ class Plan:
                                            1 if accumulate else 0, ctypes.c_void_p(st)), "omf_qsgd_decode_packed")
         return y_out
 
+    def qsgd_decode_sum_packed(self, packed_list: Sequence[torch.Tensor], levels: int, norms: Sequence[torch.Tensor],
+                               y_out: Optional[torch.Tensor] = None, init: bool = False,
+                               divisor: Optional[float] = None, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_sum_packed: ``qsgd_decode_sum`` over packed arenas (``qsgd_pack``'s layout,
+        ``packed_words(levels)`` int32 words each) — ``y = (init ? y : 0) + Σ_k decode(packed_list[k],
+        norms[k])`` in list order, then ``/ divisor``, each packed payload read once and ``y`` written
+        once.  Same bytes as ``qsgd_decode_sum`` on the levels unpacked; ``init`` and ``divisor`` as there."""
+        levels = int(levels)
+        packed_list, norms = list(packed_list), list(norms)
+        if not packed_list or len(packed_list) != len(norms):
+            raise ValueError("qsgd_decode_sum_packed needs one norm tensor per payload and at least one "
+                             f"({len(packed_list)}, {len(norms)})")
+        dev = self.device
+        words = self.packed_words(levels)  # raises on levels outside the packed wire's range
+        for k, (p, nm) in enumerate(zip(packed_list, norms)):
+            _need(p, f"packed_list[{k}]", torch.int32, dev, words, 4)
+            _need(nm, f"norms[{k}]", torch.float32, dev, self.nt, 4)
+        if y_out is None:
+            if init:
+                raise ValueError("init=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        n = len(packed_list)
+        pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
+        npp = (ctypes.c_void_p * n)(*[nm.data_ptr() for nm in norms])
+        st = stream if stream is not None else _stream(dev)
+        check(lib().omf_qsgd_decode_sum_packed(self._h, pp, npp, n, levels, _ptr(y_out), 1 if init else 0, d,
+                                               ctypes.c_void_p(st)), "omf_qsgd_decode_sum_packed")
+        return y_out
+
     # ------------------------------------------------------------ Top-K
     def topk_ks(self, ratio: float) -> List[int]:
         return list(self._topk_geom(ratio)[0])

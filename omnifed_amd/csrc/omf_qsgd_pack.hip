@@ -195,6 +195,159 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
   }
 }
 
+// N clients' packed payloads decoded and summed in one pass (omf_qsgd_decode_sum_packed), in
+// qsgd_decode_packed's shape: one workgroup per 8 Ki-element block, one 32-element group per thread.
+//   s = init ? y : +0;  s = fl32(s + fl32(fl32(norm_c[t] * (code_c - L)) / levels))  c = 0..N-1;
+//   y = divisor != 0 ? s / divisor : s
+// the bytes of omf_qsgd_decode_sum on the same levels unpacked.  All N clients' b words of the
+// thread's group go out first (unconditional, clamped to the packed arena's last group), with the
+// block's table entry and the N norms in flight; the 32 running sums stay in registers, added in
+// client order.  With `init` the sums start from y, which is read as lane-contiguous 16-byte loads
+// and brought into group order through the 33-word-row tile (fp32 addition does not let y be added
+// last); the sums leave through the same tile as lane-contiguous non-temporal 16-byte stores.
+// The client pointers are kernel arguments indexed at compile time (N is a template parameter: a
+// runtime index into a by-value array is copied to scratch).  A block not inside one tensor finds
+// each group's tensor and goes element by element where a tensor ends inside a quad; with `fill`
+// it also writes the padding of [0, arena_end) (fl32(+0 / pad_div), or +0), otherwise padding is
+// neither read nor written.
+// B: compile-time code width (2..10), or 0 = the runtime width b_rt, whose codes are read from
+// memory element by element (a register array indexed by a runtime word count goes to scratch).
+constexpr int kPackedSumMax = 8;     // clients per launch; omf_qsgd_decode_sum_packed chains groups
+constexpr int kPackedSumMaxWide = 4; // the same for the runtime-width instance (32 * N unrolled two-word reads)
+template <int N>
+struct PackedSumArgs {
+  const uint32_t* packed[N];
+  const float* norm[N];
+  float* y;
+  float levels;      // fl32(levels)
+  float inv_levels;  // 1 / levels for a power of two (exact), else unused
+  float divisor;     // 0: no division
+  float pad_div;     // the whole call's divisor: what the padding is divided by (fill)
+  int32_t init;      // the sum starts from y (else from +0: y is not read)
+  int32_t fill;      // padding elements of [0, arena_end) are written
+  int32_t L;
+  int32_t b_rt;
+};
+
+template <int B, bool POW2, int N>
+__global__ __launch_bounds__(kThreads) void qsgd_decode_sum_packed(PackedSumArgs<N> a,
+                                                                   const uint32_t* __restrict__ binfo, int64_t nbinfo,
+                                                                   const int64_t* __restrict__ begins,
+                                                                   const int64_t* __restrict__ sizes, int32_t nt,
+                                                                   int64_t arena_end) {
+  constexpr int G = kGroupBlk;
+  __shared__ float tile[kThreads * 33];
+  __shared__ int32_t s_lim[kThreads];
+  const int b = B ? B : a.b_rt;
+  const int64_t base = (int64_t)blockIdx.x * G;
+  const int64_t e0 = base + 32 * (int64_t)threadIdx.x;
+  // unconditional loads, clamped to the packed arena's last group
+  const int64_t woff = min(e0 >> 5, (arena_end - 1) >> 5) * (int64_t)b;
+  uint32_t wd[N][B ? B : 1];
+  if (B) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+#pragma unroll
+      for (int i = 0; i < (B ? B : 1); ++i) wd[c][i] = __builtin_nontemporal_load(a.packed[c] + woff + i);
+    }
+  }
+  bool whole;  // uniform: from the block's two table entries
+  int32_t t;
+  int lim = group_tensor(binfo, nbinfo, begins, sizes, nt, e0, &whole, &t);
+  if (!whole) {
+    if (e0 < begins[t]) lim = 0;  // padding before the first tensor
+    s_lim[threadIdx.x] = lim;
+    __syncthreads();
+  }
+  float nrm[N];
+#pragma unroll
+  for (int c = 0; c < N; ++c) nrm[c] = lim > 0 ? a.norm[c][t] : 0.0f;
+  float s[32];
+  if (a.init) {  // uniform
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      const int e = 4 * (v * kThreads + (int)threadIdx.x);  // element of this block
+      const int l = whole ? 4 : s_lim[e >> 5] - (e & 31);   // elements of the quad inside a tensor
+      const float* yi = a.y + base + e;
+      f32x4_t pv = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (l >= 4) {
+        pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(yi));
+      } else {
+        if (l > 0) pv[0] = yi[0];
+        if (l > 1) pv[1] = yi[1];
+        if (l > 2) pv[2] = yi[2];
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) tile[((e + c) >> 5) * 33 + ((e + c) & 31)] = pv[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 32; ++i) s[i] = tile[threadIdx.x * 33 + i];  // this thread's row: rewritten by it alone below
+  } else {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) s[i] = 0.0f;
+  }
+  const uint64_t mask = (1ull << b) - 1ull;
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    uint64_t acc = 0;
+    int nb = 0, w = 0;
+    const uint32_t* p = a.packed[c] + woff;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      uint32_t code;
+      if (B) {
+        if (nb < b) {
+          acc |= (uint64_t)wd[c][w++] << nb;
+          nb += 32;
+        }
+        code = (uint32_t)(acc & mask);
+        acc >>= b;
+        nb -= b;
+      } else {  // bits [i b, (i + 1) b) of the group's b words: at most two words, both inside the group
+        const int bit = i * b, wi = bit >> 5;
+        const uint64_t two = ((uint64_t)p[min(wi + 1, b - 1)] << 32) | p[wi];
+        code = (uint32_t)((two >> (bit & 31)) & mask);
+      }
+      const int32_t qi = (int32_t)(code - (uint32_t)a.L);
+      const float nq = __fmul_rn(nrm[c], (float)qi);  // qsgd_decode_arena's arithmetic
+      s[i] = __fadd_rn(s[i], POW2 ? __fmul_rn(nq, a.inv_levels) : nq / a.levels);
+    }
+    // One client at a time: the sums are pinned in their registers here.  Left free, the compiler sinks
+    // every client's unpack and adds to the end and holds all their codes at once (256 VGPRs, one
+    // wave per SIMD at N = 8).
+#pragma unroll
+    for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(s[i]));
+  }
+  if (a.divisor != 0.0f) {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) s[i] = s[i] / a.divisor;
+  }
+#pragma unroll
+  for (int i = 0; i < 32; ++i) tile[threadIdx.x * 33 + i] = s[i];
+  __syncthreads();
+  const float pad = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const int e = 4 * (v * kThreads + (int)threadIdx.x);
+    float f[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) f[c] = tile[((e + c) >> 5) * 33 + ((e + c) & 31)];
+    float* yo = a.y + base + e;
+    const int l = whole ? 4 : s_lim[e >> 5] - (e & 31);
+    if (l >= 4) {
+      store_nt(yo, make_float4(f[0], f[1], f[2], f[3]));
+    } else if (a.fill && base + e + 4 <= arena_end) {  // a quad with padding, all of it inside the arena
+      store_nt(yo, make_float4(l > 0 ? f[0] : pad, l > 1 ? f[1] : pad, l > 2 ? f[2] : pad, pad));
+    } else {
+      for (int c = 0; c < 4; ++c) {
+        if (c < l) yo[c] = f[c];
+        else if (a.fill && base + e + c < arena_end) yo[c] = pad;
+      }
+    }
+  }
+}
+
 // The plan's arena as the pack and the decode walk it.
 struct ArenaArgs {
   const uint32_t* binfo;
@@ -246,6 +399,69 @@ void dispatch_decode(int b, dim3 g, hipStream_t st, const uint32_t* packed, cons
     default: OMF_DP(0); break;
   }
 #undef OMF_DP
+}
+
+// ---- omf_qsgd_decode_sum_packed: one group of at most kPackedSumMax clients per launch
+struct PackedSumCall {
+  ArenaArgs a;
+  dim3 grid;
+  const uint32_t* const* packed;
+  const float* const* norm;
+  float* y;
+  float levels, inv_levels, divisor, pad_div;
+  int32_t init, fill, L, b;
+  hipStream_t st;
+};
+
+template <int B, bool P, int N>
+void launch_psum_n(const PackedSumCall& c) {
+  PackedSumArgs<N> k{};
+  for (int i = 0; i < N; ++i) { k.packed[i] = c.packed[i]; k.norm[i] = c.norm[i]; }
+  k.y = c.y; k.levels = c.levels; k.inv_levels = c.inv_levels; k.divisor = c.divisor; k.pad_div = c.pad_div;
+  k.init = c.init; k.fill = c.fill; k.L = c.L; k.b_rt = c.b;
+  hipLaunchKernelGGL((qsgd_decode_sum_packed<B, P, N>), c.grid, dim3(kThreads), 0, c.st, k, c.a.binfo, c.a.nbinfo,
+                     c.a.begins, c.a.sizes, c.a.nt, c.a.arena_end);
+}
+
+template <int B, bool P>
+void launch_psum(const PackedSumCall& c, int n) {
+  static_assert(kPackedSumMax == 8 && kPackedSumMaxWide == 4, "one case per group size");
+  if constexpr (B != 0) {
+    switch (n) {
+      case 5: launch_psum_n<B, P, 5>(c); return;
+      case 6: launch_psum_n<B, P, 6>(c); return;
+      case 7: launch_psum_n<B, P, 7>(c); return;
+      case 8: launch_psum_n<B, P, 8>(c); return;
+      default: break;
+    }
+  }
+  switch (n) {
+    case 1: launch_psum_n<B, P, 1>(c); break;
+    case 2: launch_psum_n<B, P, 2>(c); break;
+    case 3: launch_psum_n<B, P, 3>(c); break;
+    default: launch_psum_n<B, P, 4>(c); break;
+  }
+}
+
+template <bool P>
+void dispatch_psum(const PackedSumCall& c, int n) {
+  switch (c.b) {
+    case 2: launch_psum<2, P>(c, n); break;
+    case 3: launch_psum<3, P>(c, n); break;
+    case 4: launch_psum<4, P>(c, n); break;
+    case 5: launch_psum<5, P>(c, n); break;
+    case 6: launch_psum<6, P>(c, n); break;
+    case 7: launch_psum<7, P>(c, n); break;
+    case 8: launch_psum<8, P>(c, n); break;
+    case 9: launch_psum<9, P>(c, n); break;
+    case 10: launch_psum<10, P>(c, n); break;
+    default: launch_psum<0, P>(c, n); break;
+  }
+}
+
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
 }
 
 }  // namespace
@@ -323,6 +539,46 @@ int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t level
   }
 #undef OMF_DD
   OMF_HIP(hipGetLastError());
+  return OMF_OK;
+}
+
+int omf_qsgd_decode_sum_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* norm,
+                               int32_t nclients, int32_t levels, float* y, int32_t init, float divisor, void* stream) {
+  if (nclients < 1) return fail(OMF_EINVAL, "omf_qsgd_decode_sum_packed: nclients must be >= 1");
+  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
+  const int32_t b = omf_qsgd_packed_bits(levels);
+  if (b < 0 || b > 32) return fail(OMF_EINVAL, "levels must be in [1, 2^31 - 1)");
+  if (!packed || !norm || !y) return fail(OMF_EINVAL, "packed, norm and y_out must be non-NULL");
+  if ((uintptr_t)y & 15) return fail(OMF_EINVAL, "y_out must be 16-byte aligned");
+  PackedSumCall c;
+  if (const int rc = packed_arena(plan, &c.a, &c.grid)) return rc;
+  const size_t ybytes = (size_t)plan->arena_end * 4;
+  const size_t pbytes = (size_t)((plan->arena_end + 31) / 32) * (size_t)b * 4;
+  for (int32_t k = 0; k < nclients; ++k) {
+    if (!packed[k] || !norm[k]) return fail(OMF_EINVAL, "omf_qsgd_decode_sum_packed: a NULL entry in packed or norm");
+    if ((uintptr_t)packed[k] & 3) return fail(OMF_EINVAL, "a packed arena must be 4-byte aligned");
+    if (overlaps(y, ybytes, packed[k], pbytes) || overlaps(y, ybytes, norm[k], (size_t)plan->nt * 4))
+      return fail(OMF_EINVAL, "omf_qsgd_decode_sum_packed: y_out overlaps a packed or norm buffer");
+  }
+  DeviceGuard g(plan->device);
+  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
+  const bool pow2 = (levels & (levels - 1)) == 0;
+  c.y = y; c.st = (hipStream_t)stream; c.L = levels; c.b = b;
+  c.levels = (float)levels;
+  c.inv_levels = pow2 ? 1.0f / (float)levels : 0.0f;  // exact for a power of two
+  // Groups of at most `per` clients, chained: later groups start from y, the first fills the
+  // padding, the last divides (omf_qsgd_decode_sum's rules).
+  const int32_t per = b <= 10 ? kPackedSumMax : kPackedSumMaxWide;
+  for (int32_t k0 = 0; k0 < nclients; k0 += per) {
+    const int n = std::min<int32_t>(per, nclients - k0);
+    c.packed = packed + k0; c.norm = norm + k0;
+    c.init = (k0 > 0 || init) ? 1 : 0;
+    c.fill = (k0 == 0 && !init) ? 1 : 0;
+    c.divisor = k0 + n == nclients ? divisor : 0.0f;
+    c.pad_div = divisor;
+    if (pow2) dispatch_psum<true>(c, n); else dispatch_psum<false>(c, n);
+    OMF_HIP(hipGetLastError());
+  }
   return OMF_OK;
 }
 

@@ -11,7 +11,8 @@ progress waits up to 10 s for it (:193-205).  Exceptions become ``success=False`
 
 The difference is where the work runs: the accumulator is a ``DeviceAggregator`` arena on the
 GPU, each update's layers are checked, staged and decoded into it in one launch per
-(width, level) (QSGD) and one scatter-add (Top-K) — the reference's ``decode_updates_dict`` then
+(width, level) (QSGD, on the reference's int8/int32 wire or the opt-in bit-packed one a leader
+with ``packed_wire`` sends) and one scatter-add (Top-K) — the reference's ``decode_updates_dict`` then
 ``acc[name] += update`` (:147-153) — and the average is one division launch (:155-171).
 ``model``'s parameters receive the average (``param.data``, or ``param.grad`` in gradients mode)
 on their own device and dtype, as the reference's ``param.data = avg_update``.

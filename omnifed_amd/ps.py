@@ -7,6 +7,9 @@ every client's ``LayerState`` list is decoded straight into one fp32 accumulator
 arena (``omf_qsgd_decode`` with accumulate=1: acc += norm·q/L in one launch for all
 QSGD tensors; Top-K layers scatter-add; dense layers add), then divided by the
 total sample count.  Clients are summed in call (= arrival) order, as the reference.
+Updates on the opt-in bit-packed QSGD wire (``QSGDBitPackedCompression``) are accepted
+too: staged as one packed arena and decoded without unpacking (``omf_qsgd_decode_packed``
+per update, ``omf_qsgd_decode_sum_packed`` per run of them in ``accumulate_many``).
 
 Several GPUs of one node (one synthetic client per rank) — the
 weighted sum Σ_i decode(Q(w_i·x_i)) / Σ_i w_i is the path's only exchange step:
@@ -87,6 +90,10 @@ class GpuOps:
         """Σ_k decode(qs[k], norms[k]) in list order (from ``y`` when ``init``), ``/ divisor``: one pass."""
         return self.plan.qsgd_decode_sum(qs, width, levels, norms, y_out=y, init=init, divisor=divisor)
 
+    def decode_sum_packed(self, packed_list, levels, norms, y, init, divisor):
+        """``decode_sum`` over packed arenas (the opt-in bit-packed wire): one pass, same bytes."""
+        return self.plan.qsgd_decode_sum_packed(packed_list, levels, norms, y_out=y, init=init, divisor=divisor)
+
     def topk_encode(self, x, ratio, residual, residual_mode, alpha, values=None, indices=None, tie_order="torch"):
         """The client's Top-K encode (the reference's selection where magnitudes tie: tie_order)."""
         values, indices, _ = self.plan.topk_encode(x, ratio, residual=residual, residual_mode=residual_mode,
@@ -155,10 +162,14 @@ class DeviceAggregator:
 
     def _stage_update(self, layers):
         """Validate one update and stage its payloads in the device; the accumulator is not touched.
-        Returns ``(q_args, t_args, adds)``: the QSGD arena ``(payload, width, level, norms)`` or None,
-        the Top-K selection ``(counts, values, indices)`` or None, and ``(name, tensor)`` dense terms."""
-        from .hybrid.communicator.global_grpc_compression import (_decode_topk_layer, _validate_layer,
-                                                                  check_topk_indices, stage_topk)
+        Returns ``(q_args, t_args, adds)``: the QSGD arena ``(payload, width, level, norms, packed)`` or
+        None, the Top-K selection ``(counts, values, indices)`` or None, and ``(name, tensor)`` dense terms.
+        ``packed``: the update's QSGD layers are ``QSGDBitPackedCompression`` ones, ``payload`` is the
+        packed arena (``qsgd_pack``'s layout, tensor t at byte ``offsets[t] * b / 8``) and ``width`` the
+        code's bits; an update's QSGD layers are all packed or all plain."""
+        from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
+                                                                  _validate_layer, check_topk_indices, stage_topk)
+        from .hybrid.compression import QSGD_PACKED_COMPRESSION_NAME
 
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
@@ -170,36 +181,54 @@ class DeviceAggregator:
             if got is not None:
                 topk_payload[L.layer_name] = got
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
-        qsgd = [L for L in kept if L.compression_type == "QSGDQuantCompression"]
+        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", "")
+        qsgd = [L for L in kept if L.compression_type in known[:2]]
         topk = [L for L in kept if L.compression_type == "TopKCompression"]
         dense = [L for L in kept if L.compression_type == ""]
-        if any(L.compression_type not in ("QSGDQuantCompression", "TopKCompression", "") for L in kept):
-            bad = next(L for L in kept if L.compression_type not in ("QSGDQuantCompression", "TopKCompression", ""))
+        if any(L.compression_type not in known for L in kept):
+            bad = next(L for L in kept if L.compression_type not in known)
             raise ValueError(f"Unsupported compression_type={bad.compression_type!r}")
         # --- stage and check everything
         q_args = None
         if qsgd:
             width, level = qsgd[0].width, qsgd[0].level
-            if any(L.width != width or L.level != level for L in qsgd):
+            packed = qsgd[0].compression_type == QSGD_PACKED_COMPRESSION_NAME  # width: the code's bits
+            if any(L.width != width or L.level != level or (L.compression_type == QSGD_PACKED_COMPRESSION_NAME) != packed
+                   for L in qsgd):
                 raise ValueError("mixed QSGD width/level within one update")
-            isz = width // 8
             norms = np.zeros(self.plan.nt, dtype=np.float32)  # absent tensors: norm 0 adds +0
             items = []
             for L in qsgd:
                 i = self.index[L.layer_name]
                 norms[i] = np.frombuffer(L.meta_tensor, dtype=np.float32).reshape(-1)[0]
-                items.append((self.plan.offsets[i] * isz, (lambda L=L: L.values_data)))
+                # plain: tensor t at byte offsets[t] * width / 8; packed: at offsets[t] * b / 8 (qsgd_pack's arena)
+                items.append((self.plan.offsets[i] * width // 8, (lambda L=L: L.values_data)))
 
-            def check(k, payload):
-                n = self.plan.sizes[self.index[qsgd[k].layer_name]]
-                if len(payload) != n * isz:
-                    raise ValueError(f"QSGD layer {qsgd[k].layer_name!r}: {len(payload) // isz} values, expected {n}")
+            if packed:
+                def check(k, payload):
+                    _check_qsgd_payload(qsgd[k], payload)  # against the layer's own shape
+                    n = self.plan.sizes[self.index[qsgd[k].layer_name]]
+                    if len(payload) != (n * width + 7) // 8:
+                        raise ValueError(f"packed QSGD layer {qsgd[k].layer_name!r}: {len(payload)} bytes, "
+                                         f"expected {(n * width + 7) // 8} for {n} values")
 
-            qd = torch.empty(self.plan.payload_elems(width), dtype=torch.int8 if width == 8 else torch.int32,
-                             device=self.device)
+                words = self.plan.packed_words(level)
+                qd = torch.empty(words, dtype=torch.int32, device=self.device)
+                total = 4 * words
+            else:
+                isz = width // 8
+
+                def check(k, payload):
+                    n = self.plan.sizes[self.index[qsgd[k].layer_name]]
+                    if len(payload) != n * isz:
+                        raise ValueError(f"QSGD layer {qsgd[k].layer_name!r}: {len(payload) // isz} values, expected {n}")
+
+                qd = torch.empty(self.plan.payload_elems(width), dtype=torch.int8 if width == 8 else torch.int32,
+                                 device=self.device)
+                total = isz * self.plan.payload_elems(width)
             nd = torch.from_numpy(norms).to(self.device)
-            hostio.bytes_to_device(items, qd, isz * self.plan.payload_elems(width), key="ps_decode", check=check)
-            q_args = (qd, width, level, nd)
+            hostio.bytes_to_device(items, qd, total, key="ps_decode", check=check)
+            q_args = (qd, width, level, nd, packed)
         t_args = None
         # a Top-K layer with more values than its tensor's elements repeats indices: decoded alone
         # with numpy's last-wins rule (_decode_topk_layer), as decode_updates_dict does
@@ -240,8 +269,11 @@ class DeviceAggregator:
         if q_args is not None:
             # Tensors absent from this update keep acc += (0 * q)/L = +0 (whatever q holds there:
             # any int8 / int32 level times a zero norm is a zero).
-            qd, width, level, nd = q_args
-            self.plan.qsgd_decode(qd, width, level, nd, y_out=self.acc, accumulate=True)
+            qd, width, level, nd, packed = q_args
+            if packed:
+                self.plan.qsgd_decode_packed(qd, level, nd, y_out=self.acc, accumulate=True)
+            else:
+                self.plan.qsgd_decode(qd, width, level, nd, y_out=self.acc, accumulate=True)
         if t_args is not None:
             self.plan.topk_decode_counts(*t_args, y=self.acc, mode=2)
         for name, arr in adds:
@@ -256,7 +288,9 @@ class DeviceAggregator:
         Updates are staged in order.  Consecutive updates that hold only QSGD layers of one
         ``(width, level)`` form a run of at most ``max_batch``, applied by ONE
         ``qsgd_decode_sum(init=True)`` over their staged payload arenas (omf_qsgd_decode_sum: faster than
-        the per-update decode at every run length measured).  An update that also holds Top-K
+        the per-update decode at every run length measured).  Updates on the packed wire
+        form runs of their own, by level, applied by ONE ``qsgd_decode_sum_packed(init=True)`` (measured
+        the same way); a plain run and a packed run never merge.  An update that also holds Top-K
         or dense layers ends the run and is applied as ``accumulate_layers`` applies it.  If staging
         update j raises, the updates before it are applied and counted, then the exception propagates:
         the accumulator holds exactly what j - 1 ``accumulate_layers`` calls would have left.  Same
@@ -270,9 +304,13 @@ class DeviceAggregator:
             run.clear()
             if not batch:
                 return
-            _, width, level, _ = batch[0][0]
-            self.plan.qsgd_decode_sum([b[0][0] for b in batch], width, level, [b[0][3] for b in batch],
-                                      y_out=self.acc, init=True)
+            _, width, level, _, packed = batch[0][0]
+            if packed:
+                self.plan.qsgd_decode_sum_packed([b[0][0] for b in batch], level, [b[0][3] for b in batch],
+                                                 y_out=self.acc, init=True)
+            else:
+                self.plan.qsgd_decode_sum([b[0][0] for b in batch], width, level, [b[0][3] for b in batch],
+                                          y_out=self.acc, init=True)
             self.update_count += len(batch)
             self.total_samples += sum(int(ns) for _, ns in batch)
 
@@ -281,7 +319,7 @@ class DeviceAggregator:
                 staged = self._stage_update(layers)
                 q_args, t_args, adds = staged
                 if q_args is not None and t_args is None and not adds:
-                    if run and (run[0][0][1:3] != q_args[1:3] or len(run) >= max_batch):
+                    if run and (run[0][0][1:3] != q_args[1:3] or run[0][0][4] != q_args[4] or len(run) >= max_batch):
                         flush()
                     run.append((q_args, number_samples))
                 else:
