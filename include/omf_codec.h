@@ -272,7 +272,11 @@ int omf_qsgd_decode_sum(omf_plan* plan, const void* const* q, const float* const
  * omf_qsgd_pack: payload (width 8 or 32, as omf_qsgd_encode wrote it) -> packed arena (8-byte
  * aligned: even widths are stored as 8-byte word pairs; omf_qsgd_decode_packed needs 4).
  * omf_qsgd_decode_packed: y = fl32(fl32(norm * (code - L)) / L), bit-identical to
- * omf_qsgd_decode of the unpacked payload (accumulate: y += that).
+ * omf_qsgd_decode of the unpacked payload (accumulate: y += that).  A code above 2L, which no
+ * encoder makes, decodes by the same formula with code - L taken as int32 (modulo 2^32; the
+ * reduction only matters at b = 32); omf_qsgd_decode_sum_packed does the same.
+ * levels: 1 <= L < 2^31 - 1, so b <= 32 (omf_qsgd_packed_bits returns -1 outside that range, and
+ * the calls OMF_EINVAL).
  */
 int32_t omf_qsgd_packed_bits(int32_t levels);
 int omf_qsgd_pack(omf_plan* plan, const void* q, int32_t width, int32_t levels, uint32_t* packed, void* stream);

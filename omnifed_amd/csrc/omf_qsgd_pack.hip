@@ -30,7 +30,8 @@ static_assert(kGroupBlk == 2 * kTableBlk, "two table blocks per workgroup");
 // A thread's 32-element group: the whole workgroup inside one tensor (both table blocks marked
 // inside the same tensor), or the group's own tensor found from the block's first one (offsets
 // are multiples of 32: a group never spans two tensors).  Returns the elements of the group in
-// its tensor (0 = padding, or past the arena) and that tensor.
+// its tensor (0 = padding, the gap in front of the first tensor included, or past the arena) and
+// that tensor.
 __device__ __forceinline__ int group_tensor(const uint32_t* __restrict__ binfo, int64_t nbinfo,
                                             const int64_t* __restrict__ begins, const int64_t* __restrict__ sizes,
                                             int32_t nt, int64_t e0, bool* whole, int32_t* tensor) {
@@ -45,6 +46,7 @@ __device__ __forceinline__ int group_tensor(const uint32_t* __restrict__ binfo, 
   }
   while (t + 1 < nt && e0 >= begins[t + 1]) ++t;
   *tensor = t;
+  if (e0 < begins[t]) return 0;  // padding before the first tensor
   const int64_t lim = min((int64_t)32, begins[t] + sizes[t] - e0);
   return lim > 0 ? (int)lim : 0;
 }
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_pack(const void* __restrict__ q
   int nb = 0, w = 0;
 #pragma unroll
   for (int i = 0; i < 32; ++i) {
-    acc |= (uint64_t)(uint32_t)(lv[i] + L) << nb;
+    acc |= (uint64_t)((uint32_t)lv[i] + (uint32_t)L) << nb;  // modulo 2^32: q + L passes INT32_MAX from L = 2^30 on
     nb += b;
     if (nb >= 32) {
       if (B) wd[w++] = (uint32_t)acc;  // static index once unrolled
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
       acc |= (uint64_t)wd[w++] << nb;
       nb += 32;
     }
-    const int32_t qi = (int32_t)(acc & mask) - L;
+    const int32_t qi = (int32_t)((uint32_t)(acc & mask) - (uint32_t)L);  // modulo 2^32 (b = 32: codes above INT32_MAX)
     acc >>= b;
     nb -= b;
     const float nq = __fmul_rn(nrm, (float)qi);  // qsgd_decode_arena's arithmetic
@@ -253,9 +255,8 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_sum_packed(PackedSumArgs
   }
   bool whole;  // uniform: from the block's two table entries
   int32_t t;
-  int lim = group_tensor(binfo, nbinfo, begins, sizes, nt, e0, &whole, &t);
+  const int lim = group_tensor(binfo, nbinfo, begins, sizes, nt, e0, &whole, &t);
   if (!whole) {
-    if (e0 < begins[t]) lim = 0;  // padding before the first tensor
     s_lim[threadIdx.x] = lim;
     __syncthreads();
   }
@@ -488,7 +489,7 @@ int packed_arena(const omf_plan* plan, ArenaArgs* a, dim3* grid) {
 extern "C" {
 
 int32_t omf_qsgd_packed_bits(int32_t levels) {
-  if (levels <= 0) return -1;
+  if (levels <= 0 || levels == INT32_MAX) return -1;  // the wire's levels: [1, 2^31 - 1), as the binding's
   const uint64_t codes = 2ull * (uint64_t)levels + 1ull;
   int32_t b = 0;
   while ((1ull << b) < codes) ++b;
