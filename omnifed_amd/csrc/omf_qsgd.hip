@@ -1,11 +1,12 @@
-// omf_qsgd.hip — QSGD encode / decode for the hybrid global hop, MI355X (gfx950).
+// omf_qsgd.hip — the QSGD plan, encoders and PS steps for the hybrid global hop, MI355X (gfx950).
 //
 // Semantics: SURVEY.md §8a "Exact QSGD semantics", restating
 //   src/omnifed/hybrid/compression/qsgd.py:36-96 (reference, Python/torch CPU).
 //
 // Kernel map (the bracketed single-read encoder, strategy 3, is omf_qsgd_bracket.hip
 // and the single-read ring encoder omf_qsgd_ring.hip; the device steps the encoders share are
-// omf_qsgd_enc.h).  Every encoder writes the same payload bits for the same norm.
+// omf_qsgd_enc.h; the decoders, the K-client sum and the flat divide are omf_qsgd_recv.hip).  Every
+// encoder writes the same payload bits for the same norm.
 //   qsgd_encode_ordered    ticket-ordered encoder (strategies 0 and 1, and every norms-only pass): one
 //                          launch for every tensor.  Work items are taken in ticket order (an atomic
 //                          counter, so a workgroup only waits on items that are already running):
@@ -17,24 +18,19 @@
 //   qsgd_quant_sub         norms supplied by the caller: one pass over the flat items, no hand-off.
 //   qsgd_encode_grid       grid encoder (strategy 4, small arenas): one workgroup per CU, x held in
 //                          registers across one grid-wide barrier.
-//   qsgd_decode_arena      y = (norm * q) / L over the arena's 4 Ki blocks, optionally accumulated (PS);
-//   qsgd_decode_flat       the same per flat item with byte loads: payloads of fewer than 4 elements.
-//   qsgd_decode_sum_arena, qsgd_decode_sum_tiny
-//                          up to 8 clients' payloads decoded and summed in one pass (omf_qsgd_decode_sum).
-//   div_f32_kernel         y /= d over a flat buffer (omf_div_f32).
 //   items_f32_kernel       dst = src / d or src over the tensors' elements only (the in-place PS step,
 //                          the last client's two-call fallback): arena padding is never written.
 //
 // Host side (the end of the file): omf_plan_create / upload_plan carve the plan's device block from
 // the tables of omf_plan_layout.cpp; encode_launch asks choose_encoder (omf_plan_layout.h) which
 // encoder serves a call and switches over five launchers (caller norms, grid, bracket — omf_bracket.h —,
-// ring — omf_ring.h —, ordered); decode_blocks launches the decoders.  struct omf_plan is in omf_plan.h.
+// ring — omf_ring.h —, ordered); the omf_ps_* steps are that switch and, where the bracketed encoder does not
+// take the last client's payload itself, omf_qsgd_decode (omf_qsgd_recv.hip).  struct omf_plan is in omf_plan.h.
 //
 // HBM-bound; no MFMA (no contraction).  Coalesced 16 B/lane fp32 loads, non-temporal
 // 16 B/lane fp32 and 4 B/lane int8 payload stores.
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "../../include/omf_codec.h"
@@ -42,6 +38,7 @@
 #include "omf_bracket.h"
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_qsgd_dec.h"
 #include "omf_qsgd_enc.h"
 #include "omf_ring.h"
 
@@ -50,18 +47,7 @@ using namespace omf::plan_layout;  // the table records and layout constants (om
 
 namespace {
 
-constexpr int kV = 16;  // float4 per thread per sub-chunk
-static_assert(kSub == (int64_t)kV * kThreads * 4, "a flat item is one sub-chunk of a 256-thread workgroup");
 static_assert(kBlkWaves == kWaves, "one wave partial per wave of a block's workgroup");
-
-struct DecArgs {
-  const void* q;
-  const float* norm;
-  float* y;
-  const Item* items;
-  float levels;      // fl32(levels)
-  float inv_levels;  // 2^-s when levels is a power of two (exact), else unused
-};
 
 // ---------------------------------------------------------------- norm hand-off
 
@@ -420,199 +406,6 @@ __global__ __launch_bounds__(1024) void qsgd_encode_grid(GridArgs a, const Item*
   }
 }
 
-// Decode one sub-chunk [b, end): y = fl32(fl32(norm * q) / L) (optionally acc += y).
-template <int WIDTH, bool ACC, bool POW2, bool FULL, int V = kV>
-__device__ __forceinline__ void decode_sub(const DecArgs& a, int64_t b, int64_t end, float norm) {
-  int32_t raw[V][WIDTH == 1 ? 1 : 4];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const int64_t e = b + 4 * ((int64_t)k * kThreads + threadIdx.x);
-    if (WIDTH == 1) {
-      const int8_t* q8 = reinterpret_cast<const int8_t*>(a.q);
-      if (FULL || e + 4 <= end) {  // streamed once: nontemporal
-        raw[k][0] = __builtin_nontemporal_load(reinterpret_cast<const int32_t*>(q8 + e));
-      } else {
-        uint32_t t = 0;
-        if (e < end) t |= (uint32_t)(uint8_t)q8[e];
-        if (e + 1 < end) t |= (uint32_t)(uint8_t)q8[e + 1] << 8;
-        if (e + 2 < end) t |= (uint32_t)(uint8_t)q8[e + 2] << 16;
-        raw[k][0] = (int32_t)t;
-      }
-    } else {
-      const int32_t* q32 = reinterpret_cast<const int32_t*>(a.q);
-      if (FULL || e + 4 <= end) {
-        const i32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(q32 + e));
-        raw[k][0] = t[0]; raw[k][1] = t[1]; raw[k][2] = t[2]; raw[k][3] = t[3];
-      } else {
-        raw[k][0] = (e < end) ? q32[e] : 0;
-        raw[k][1] = (e + 1 < end) ? q32[e + 1] : 0;
-        raw[k][2] = (e + 2 < end) ? q32[e + 2] : 0;
-        raw[k][3] = 0;
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const int64_t e = b + 4 * ((int64_t)k * kThreads + threadIdx.x);
-    if (!FULL && e >= end) continue;
-    int32_t qi[4];
-    if (WIDTH == 1) {
-      qi[0] = (int32_t)(int8_t)(raw[k][0] & 0xff);
-      qi[1] = (int32_t)(int8_t)((raw[k][0] >> 8) & 0xff);
-      qi[2] = (int32_t)(int8_t)((raw[k][0] >> 16) & 0xff);
-      qi[3] = (int32_t)(int8_t)((raw[k][0] >> 24) & 0xff);
-    } else {
-      qi[0] = raw[k][0]; qi[1] = raw[k][1]; qi[2] = raw[k][2]; qi[3] = raw[k][3];
-    }
-    // (norm * q) / 2^s == (norm * q) * 2^-s exactly (power-of-two scaling, both correctly rounded).
-    float yv[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float nq = __fmul_rn(norm, (float)qi[c]);
-      yv[c] = POW2 ? __fmul_rn(nq, a.inv_levels) : nq / a.levels;
-    }
-    float* y = a.y + e;
-    if (FULL || e + 4 <= end) {
-      float4 o = make_float4(yv[0], yv[1], yv[2], yv[3]);
-      if (ACC) {
-        const f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(y));
-        const float4 prev = make_float4(pv[0], pv[1], pv[2], pv[3]);
-        o.x = __fadd_rn(prev.x, o.x); o.y = __fadd_rn(prev.y, o.y);
-        o.z = __fadd_rn(prev.z, o.z); o.w = __fadd_rn(prev.w, o.w);
-      }
-      store_nt(y, o);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        if (e + c < end) y[c] = ACC ? __fadd_rn(y[c], yv[c]) : yv[c];
-    }
-  }
-}
-
-template <int WIDTH, bool ACC, bool POW2>
-__global__ __launch_bounds__(kThreads) void qsgd_decode_flat(DecArgs a) {
-  const Item it = a.items[blockIdx.x];
-  const float norm = a.norm[it.tensor];
-  for (int64_t b = it.begin; b < it.end; b += kSub) {
-    const int64_t end = min(b + kSub, it.end);
-    if (end - b == kSub) decode_sub<WIDTH, ACC, POW2, true>(a, b, end, norm);
-    else decode_sub<WIDTH, ACC, POW2, false>(a, b, end, norm);
-  }
-}
-
-// Decoder over arena-aligned blocks: the payload loads depend on blockIdx only, so they go out
-// at once; the block's tensor (binfo, one entry per 4 Ki-element table block: tensor id, bit 31 =
-// the table block lies inside it) and its norm are scalar loads in flight with them.  A block in
-// a table block that crosses a tensor boundary or padding (at most nt + 1 of them) finds each
-// quad's tensor and writes only its elements.  Round 5: the decode block is narrower than the
-// table block — kDecQuads(W, ACC) quads per thread: 2 for an int8 payload, 1 for an int32 payload
-// or an accumulate — measured on Llama-400M (interleaved): int8
-// 0.298-0.304 ms against 0.331 with 4 quads, int32 0.492 against 0.550, accumulate 0.556 / 0.748
-// against 0.612 / 0.807 (fewer bytes per thread, more workgroups in flight per CU).
-static_assert(kDecBlk == (int64_t)4 * kThreads * 4, "4096 elements per binfo table block");
-template <int WIDTH, bool ACC>
-constexpr int kDecQuads = (WIDTH == 1 && !ACC) ? 2 : 1;
-
-template <int WIDTH, bool ACC, bool POW2>
-__device__ __forceinline__ void dec_quad(const DecArgs& a, int32_t raw[4], float norm, float (&yv)[4]) {
-  int32_t qi[4];
-  if (WIDTH == 1) {
-    qi[0] = (int32_t)(int8_t)(raw[0] & 0xff);
-    qi[1] = (int32_t)(int8_t)((raw[0] >> 8) & 0xff);
-    qi[2] = (int32_t)(int8_t)((raw[0] >> 16) & 0xff);
-    qi[3] = (int32_t)(int8_t)((raw[0] >> 24) & 0xff);
-  } else {
-    qi[0] = raw[0]; qi[1] = raw[1]; qi[2] = raw[2]; qi[3] = raw[3];
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float nq = __fmul_rn(norm, (float)qi[c]);
-    yv[c] = POW2 ? __fmul_rn(nq, a.inv_levels) : nq / a.levels;
-  }
-}
-
-template <int WIDTH, bool ACC, bool POW2>
-__global__ __launch_bounds__(kThreads) void qsgd_decode_arena(DecArgs a, const uint32_t* __restrict__ binfo,
-                                                              const float* __restrict__ norms,
-                                                              const int64_t* __restrict__ begins,
-                                                              const int64_t* __restrict__ sizes, int32_t nt,
-                                                              int64_t qlast, uint32_t blk0) {
-  constexpr int V = kDecQuads<WIDTH, ACC>;
-  const uint32_t bid = blk0 + blockIdx.x;  // a range launch starts at block blk0
-  const int64_t base = (int64_t)bid * (V * kThreads * 4);
-  int32_t raw[V][WIDTH == 1 ? 1 : 4];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {  // unconditional (clamped) loads
-    const int64_t e = min(base + 4 * ((int64_t)k * kThreads + threadIdx.x), qlast);
-    if (WIDTH == 1) {  // default policy: 0.298 against 0.304 ms non-temporal
-      raw[k][0] = *reinterpret_cast<const int32_t*>(reinterpret_cast<const int8_t*>(a.q) + e);
-    } else {
-      const i32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(reinterpret_cast<const int32_t*>(a.q) + e));
-      raw[k][0] = t[0]; raw[k][1] = t[1]; raw[k][2] = t[2]; raw[k][3] = t[3];
-    }
-  }
-  const uint32_t info = binfo[base / kDecBlk];
-  const int32_t t0 = (int32_t)(info & 0x7fffffffu);
-  if (info >> 31) {  // the whole table block lies inside tensor t0
-    const float norm = norms[t0];
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const int64_t e = base + 4 * ((int64_t)k * kThreads + threadIdx.x);
-      float yv[4];
-      dec_quad<WIDTH, ACC, POW2>(a, raw[k], norm, yv);
-      float4 o = make_float4(yv[0], yv[1], yv[2], yv[3]);
-      if (ACC) {
-        const f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(a.y + e));
-        o.x = __fadd_rn(pv[0], o.x); o.y = __fadd_rn(pv[1], o.y);
-        o.z = __fadd_rn(pv[2], o.z); o.w = __fadd_rn(pv[3], o.w);
-      }
-      store_nt(a.y + e, o);
-    }
-    return;
-  }
-  // boundary block: each quad's tensor, element by element
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const int64_t e = base + 4 * ((int64_t)k * kThreads + threadIdx.x);
-    int32_t t = t0;
-    while (t + 1 < nt && e >= begins[t + 1]) ++t;
-    const int64_t tb = begins[t], te = tb + sizes[t];
-    if (e + 3 < tb || e >= te) continue;  // padding (offsets are multiples of 4: a quad never
-                                          // starts before its tensor and ends inside it)
-    int32_t rr[4] = {raw[k][0], WIDTH == 1 ? 0 : raw[k][1], WIDTH == 1 ? 0 : raw[k][2], WIDTH == 1 ? 0 : raw[k][3]};
-    if (e + 4 > te) {  // the tensor's partial last quad: its bytes only (the payload may end here)
-      if (WIDTH == 1) {
-        const int8_t* q8 = reinterpret_cast<const int8_t*>(a.q);
-        uint32_t w = 0;
-        for (int c = 0; c < 3; ++c)
-          if (e + c < te) w |= (uint32_t)(uint8_t)q8[e + c] << (8 * c);
-        rr[0] = (int32_t)w;
-      } else {
-        const int32_t* q32 = reinterpret_cast<const int32_t*>(a.q);
-        for (int c = 0; c < 3; ++c) rr[c] = e + c < te ? q32[e + c] : 0;
-        rr[3] = 0;
-      }
-    }
-    float yv[4];
-    dec_quad<WIDTH, ACC, POW2>(a, rr, norms[t], yv);
-    for (int c = 0; c < 4; ++c)
-      if (e + c < te) a.y[e + c] = ACC ? __fadd_rn(a.y[e + c], yv[c]) : yv[c];
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void div_f32_kernel(float* __restrict__ y, int64_t n, float d) {
-  const int64_t stride = (int64_t)gridDim.x * kThreads * 4;
-  for (int64_t e = 4 * ((int64_t)blockIdx.x * kThreads + threadIdx.x); e < n; e += stride) {
-    if (e + 4 <= n) {
-      float4 v = *reinterpret_cast<float4*>(y + e);
-      v.x = v.x / d; v.y = v.y / d; v.z = v.z / d; v.w = v.w / d;
-      *reinterpret_cast<float4*>(y + e) = v;
-    } else {
-      for (int64_t i = e; i < n; ++i) y[i] = y[i] / d;
-    }
-  }
-}
-
 // dst = src / d (DIV) or src over the plan's flat items: the tensors' elements only, so the padding
 // between tensors is neither read nor written.  dst may be src.  Item starts are multiples of 4.
 template <bool DIV>
@@ -630,155 +423,11 @@ __global__ __launch_bounds__(kThreads) void items_f32_kernel(const Item* __restr
   }
 }
 
-// N clients' payloads decoded and summed in one pass (omf_qsgd_decode_sum), in qsgd_decode_arena's
-// shape: one workgroup per arena-aligned block of 1 Ki elements (one quad per thread; two for int8
-// measured the same), all N payload quads of a thread loaded at once (unconditional, clamped), the binfo entry and the N norms scalar loads in
-// flight with them, the sum in registers (client order, __fadd_rn), one non-temporal store per quad.
-//   s = init ? y : +0;  s = fl32(s + dec_quad(q_c, norm_c[t]))  c = 0..N-1;  y = divisor != 0 ? s / divisor : s
-// The client pointers are kernel arguments indexed at compile time (N is a template parameter: a
-// runtime index into a by-value array is copied to scratch).  Boundary blocks go element by element,
-// as the decoder's; with `fill` they also write the padding of [0, arena_end) (fl32(+0 / divisor), or
-// +0): the bytes of memset, N accumulating decodes and omf_div_f32 over the arena.
-constexpr int kSumMax = 8;  // clients per launch; omf_qsgd_decode_sum chains groups
-template <int N>
-struct SumArgs {
-  const void* q[N];
-  const float* norm[N];
-  float* y;
-  float levels;      // fl32(levels)
-  float inv_levels;  // as DecArgs
-  float divisor;     // 0: no division
-  float pad_div;     // the whole call's divisor: what the padding is divided by (fill)
-  int32_t init;      // the sum starts from y (else from +0: y is not read)
-  int32_t fill;      // padding elements of [0, arena_end) are written
-};
-
-constexpr int64_t kSumBlk = (int64_t)kThreads * 4;  // elements per workgroup
-static_assert(kDecBlk % kSumBlk == 0, "whole sum blocks per binfo table block");
-template <int WIDTH, bool POW2, int N>
-__global__ __launch_bounds__(kThreads) void qsgd_decode_sum_arena(SumArgs<N> a, const uint32_t* __restrict__ binfo,
-                                                                  const int64_t* __restrict__ begins,
-                                                                  const int64_t* __restrict__ sizes, int32_t nt,
-                                                                  int64_t qlast, int64_t arena_end) {
-  const int64_t base = (int64_t)blockIdx.x * kSumBlk;
-  const int64_t e = base + 4 * (int64_t)threadIdx.x;
-  const int64_t ec = min(e, qlast);  // unconditional (clamped) loads, every client's
-  int32_t raw[N][WIDTH == 1 ? 1 : 4];
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    if (WIDTH == 1) {
-      raw[c][0] = *reinterpret_cast<const int32_t*>(reinterpret_cast<const int8_t*>(a.q[c]) + ec);
-    } else {
-      const i32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(reinterpret_cast<const int32_t*>(a.q[c]) + ec));
-      raw[c][0] = t[0]; raw[c][1] = t[1]; raw[c][2] = t[2]; raw[c][3] = t[3];
-    }
-  }
-  f32x4_t pv = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (a.init) pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(a.y + ec));
-  const uint32_t info = binfo[base / kDecBlk];
-  const int32_t t0 = (int32_t)(info & 0x7fffffffu);
-  DecArgs d{};  // dec_quad reads the levels only
-  d.levels = a.levels; d.inv_levels = a.inv_levels;
-  if (info >> 31) {  // the whole table block lies inside tensor t0
-    float norm[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) norm[c] = a.norm[c][t0];
-    float s[4] = {pv[0], pv[1], pv[2], pv[3]};
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-      float yv[4];
-      dec_quad<WIDTH, false, POW2>(d, raw[c], norm[c], yv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] = __fadd_rn(s[j], yv[j]);
-    }
-    if (a.divisor != 0.0f) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] = s[j] / a.divisor;
-    }
-    store_nt(a.y + e, make_float4(s[0], s[1], s[2], s[3]));
-    return;
-  }
-  // boundary block: the quad's tensor, element by element
-  if (e >= arena_end) return;
-  const float pad = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
-  int32_t t = t0;
-  while (t + 1 < nt && e >= begins[t + 1]) ++t;
-  const int64_t tb = begins[t], te = tb + sizes[t];
-  if (e < tb || e >= te) {  // a quad of padding (offsets are multiples of 4: no tensor starts inside it)
-    if (a.fill)
-      for (int j = 0; j < 4; ++j)
-        if (e + j < arena_end) a.y[e + j] = pad;
-    return;
-  }
-  const bool part = e + 4 > te;  // the tensor's partial last quad: its bytes only (the payload may end here)
-  float s[4];
-  for (int j = 0; j < 4; ++j) s[j] = (a.init && e + j < te) ? a.y[e + j] : 0.0f;
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    int32_t rr[4] = {raw[c][0], WIDTH == 1 ? 0 : raw[c][1], WIDTH == 1 ? 0 : raw[c][2], WIDTH == 1 ? 0 : raw[c][3]};
-    if (part) {
-      if (WIDTH == 1) {
-        const int8_t* q8 = reinterpret_cast<const int8_t*>(a.q[c]);
-        uint32_t w = 0;
-        for (int j = 0; j < 3; ++j)
-          if (e + j < te) w |= (uint32_t)(uint8_t)q8[e + j] << (8 * j);
-        rr[0] = (int32_t)w;
-      } else {
-        const int32_t* q32 = reinterpret_cast<const int32_t*>(a.q[c]);
-        for (int j = 0; j < 3; ++j) rr[j] = e + j < te ? q32[e + j] : 0;
-        rr[3] = 0;
-      }
-    }
-    float yv[4];
-    dec_quad<WIDTH, false, POW2>(d, rr, a.norm[c][t], yv);
-    for (int j = 0; j < 4; ++j) s[j] = __fadd_rn(s[j], yv[j]);
-  }
-  for (int j = 0; j < 4; ++j) {
-    if (e + j < te) a.y[e + j] = a.divisor != 0.0f ? s[j] / a.divisor : s[j];
-    else if (a.fill && e + j < arena_end) a.y[e + j] = pad;
-  }
-}
-
-// The same for an arena of fewer than 4 elements (no whole quad to load): one thread per element,
-// byte / dword loads, `n` clients behind a uniform guard (compile-time indices all the same).
-template <int WIDTH, bool POW2>
-__global__ __launch_bounds__(64) void qsgd_decode_sum_tiny(SumArgs<kSumMax> a, int32_t n,
-                                                           const int64_t* __restrict__ begins,
-                                                           const int64_t* __restrict__ sizes, int32_t nt,
-                                                           int64_t arena_end) {
-  const int64_t i = threadIdx.x;
-  if (i >= arena_end) return;
-  int32_t t = -1;
-  for (int32_t u = 0; u < nt; ++u)
-    if (i >= begins[u] && i < begins[u] + sizes[u]) t = u;
-  if (t < 0) {
-    if (a.fill) a.y[i] = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
-    return;
-  }
-  DecArgs d{};
-  d.levels = a.levels; d.inv_levels = a.inv_levels;
-  float s = a.init ? a.y[i] : 0.0f;
-#pragma unroll
-  for (int c = 0; c < kSumMax; ++c) {
-    if (c < n) {
-      int32_t rr[4] = {0, 0, 0, 0};
-      rr[0] = WIDTH == 1 ? (int32_t)(uint8_t) reinterpret_cast<const int8_t*>(a.q[c])[i]
-                         : reinterpret_cast<const int32_t*>(a.q[c])[i];
-      float yv[4];
-      dec_quad<WIDTH, false, POW2>(d, rr, a.norm[c][t], yv);
-      s = __fadd_rn(s, yv[0]);
-    }
-  }
-  a.y[i] = a.divisor != 0.0f ? s / a.divisor : s;
-}
-
 }  // namespace
 
 // ====================================================================== host side
 // struct omf_plan and its stream ordering (plan_enter / plan_leave) are in omf_plan.h; the work-item
 // tables, the carve of a device allocation and the encoder choice in omf_plan_layout.h.
-
-static bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 // Allocates a carve's bytes into *block, binds its pointers and fills its regions.  On failure *block
 // and every pointer of the carve are NULL.
@@ -1325,9 +974,8 @@ int omf_ps_apply_encode(omf_plan* p, const float* acc, float divisor, float* avg
   if (!(divisor != 0.0f)) return fail(OMF_EINVAL, "omf_ps_apply_encode: divisor must be non-zero");
   if (!aligned(avg_out, 16)) return fail(OMF_EINVAL, "omf_ps_apply_encode: avg_out must be 16-byte aligned");
   const size_t bytes = 4 * (size_t)p->arena_end;
-  const uintptr_t a0 = (uintptr_t)acc, o0 = (uintptr_t)avg_out;
   const bool alias = avg_out == acc;
-  if (!alias && a0 < o0 + bytes && o0 < a0 + bytes)
+  if (!alias && overlaps(acc, bytes, avg_out, bytes))
     return fail(OMF_EINVAL, "omf_ps_apply_encode: avg_out partially overlaps acc (pass the same pointer or disjoint buffers)");
   // The fused launch reads acc while it writes avg (second-pass chunks of large tensors
   // re-read acc, the bounded-wait fallback recomputes partials from it), so it needs
@@ -1362,10 +1010,7 @@ int omf_ps_accumulate_apply_encode(omf_plan* p, const float* acc, const void* q_
       !aligned(q_in, width_in == 8 ? 4 : 16))
     return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
   const size_t bytes = 4 * (size_t)p->arena_end;
-  auto overlap = [bytes](const void* x, const void* y) {
-    const uintptr_t a0 = (uintptr_t)x, b0 = (uintptr_t)y;
-    return a0 < b0 + bytes && b0 < a0 + bytes;
-  };
+  auto overlap = [bytes](const void* x, const void* y) { return overlaps(x, bytes, y, bytes); };
   if (overlap(avg_out, acc) || (acc_out && overlap(avg_out, acc_out)) || (acc_out && acc_out != acc && overlap(acc_out, acc)))
     return fail(OMF_EINVAL, "omf_ps_accumulate_apply_encode: avg_out must be disjoint from acc and acc_out; acc_out is "
                             "acc itself or disjoint from it");
@@ -1393,183 +1038,5 @@ int omf_qsgd_norms(omf_plan* plan, const float* x, float alpha, float* norm_out,
   return encode_impl(plan, x, alpha, 0, nullptr, 0, 0, nullptr, nullptr, norm_out, true, stream);
 }
 
-static int decode_blocks(omf_plan* p, const void* q, int32_t width, int32_t levels, const float* norm, float* y,
-                         int32_t accumulate, int64_t b0, int64_t b1, void* stream) {
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
-  if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
-  if (!q || !norm || !y) return fail(OMF_EINVAL, "q, norm and y_out must be non-NULL");
-  if (!aligned(y, 16) || !aligned(q, width == 8 ? 4 : 16))
-    return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
-  DeviceGuard g(p->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  DecArgs a;
-  a.q = q; a.norm = norm; a.y = y; a.items = p->d_flat;
-  a.levels = (float)levels;
-  const bool pow2 = (levels & (levels - 1)) == 0;
-  a.inv_levels = pow2 ? 1.0f / (float)levels : 0.0f;  // exact for a power of two
-  b0 = std::max<int64_t>(b0, 0);
-  b1 = std::min<int64_t>(b1, p->n_dec_blocks);
-  if (b1 <= b0) return OMF_OK;
-  const dim3 blk(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  // A plain decode's workgroups reserve 24 KiB of LDS each (unused): six per CU — Llama-400M 0.294-
-  // 0.296 ms at s = 4 and 0.482-0.484 at s = 8 against 0.301 / 0.490 uncapped, 0.308 / 0.489 at 28 KiB
-  // (DESIGN.md §3.8); OMF_DEC_LDS overrides.  Accumulating decodes keep every wave.
-  static const size_t dlds = [] { const char* v = omf::knob("OMF_DEC_LDS"); return v ? (size_t)atoi(v) : (size_t)24576; }();
-  // the last whole quad of the payload the caller holds (width 8: round_up(arena_end, 4) bytes
-  // are not promised, so a clamped load never passes the last full quad)
-  const int64_t qlast = (p->arena_end & ~(int64_t)3) - 4;  // < 0 only for arenas of < 4 elements
-#define OMF_DEC(W, A, P)                                                                                         \
-  do {                                                                                                           \
-    if (qlast >= 0) {                                                                                            \
-      const int64_t per = kDecBlk / (kDecQuads<W, A> * kThreads * 4); /* decode blocks per table block */       \
-      hipLaunchKernelGGL((qsgd_decode_arena<W, A, P>), dim3((unsigned)((b1 - b0) * per)), blk, A ? 0 : dlds, st, a, \
-                         (const uint32_t*)p->d_dec_binfo, norm, (const int64_t*)p->d_begins,                    \
-                         (const int64_t*)p->d_sizes, p->nt, qlast, (uint32_t)(b0 * per));                       \
-    } else /* a payload of < 4 elements: the item decoder's byte loads */                                          \
-      hipLaunchKernelGGL((qsgd_decode_flat<W, A, P>), dim3((unsigned)p->n_flat), blk, 0, st, a);                \
-  } while (0)
-  if (width == 8) {
-    if (accumulate) { if (pow2) OMF_DEC(1, true, true); else OMF_DEC(1, true, false); }
-    else { if (pow2) OMF_DEC(1, false, true); else OMF_DEC(1, false, false); }
-  } else {
-    if (accumulate) { if (pow2) OMF_DEC(4, true, true); else OMF_DEC(4, true, false); }
-    else { if (pow2) OMF_DEC(4, false, true); else OMF_DEC(4, false, false); }
-  }
-#undef OMF_DEC
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
-int omf_qsgd_decode(omf_plan* p, const void* q, int32_t width, int32_t levels, const float* norm, float* y,
-                    int32_t accumulate, void* stream) {
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  return decode_blocks(p, q, width, levels, norm, y, accumulate, 0, p->n_dec_blocks, stream);
-}
-
-int omf_qsgd_decode_range(omf_plan* p, const void* q, int32_t width, int32_t levels, const float* norm, float* y,
-                          int32_t accumulate, int64_t elem_begin, int64_t elem_end, void* stream) {
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  if (elem_begin < 0 || elem_end < elem_begin) return fail(OMF_EINVAL, "omf_qsgd_decode_range: bad element range");
-  if (elem_end == elem_begin) return OMF_OK;  // an empty range overlaps no block, wherever it lies
-  if (p->arena_end < 4)  // the item decoder of tiny payloads has no block ranges: its one block, whole
-    return decode_blocks(p, q, width, levels, norm, y, accumulate, 0, elem_begin < kDecBlk ? p->n_dec_blocks : 0, stream);
-  return decode_blocks(p, q, width, levels, norm, y, accumulate, elem_begin / kDecBlk,
-                       (elem_end + kDecBlk - 1) / kDecBlk, stream);
-}
-
-int omf_div_f32(float* y, int64_t n, float divisor, void* stream) {
-  if (n < 0 || (n > 0 && !y)) return fail(OMF_EINVAL, "omf_div_f32: bad arguments");
-  if (n == 0) return OMF_OK;
-  if (!aligned(y, 16)) return fail(OMF_EINVAL, "omf_div_f32: y must be 16-byte aligned");
-  const int64_t blocks = std::min<int64_t>((n + 4 * kThreads - 1) / (4 * kThreads), 8192);
-  hipLaunchKernelGGL(div_f32_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, y, n, divisor);
-  OMF_HIP(hipGetLastError());
-  return OMF_OK;
-}
-
 }  // extern "C"
 
-// ---- omf_qsgd_decode_sum: one group of at most kSumMax clients per launch
-namespace {
-
-struct SumCall {
-  const omf_plan* p;
-  const void* const* q;
-  const float* const* norm;
-  float* y;
-  float levels, inv_levels, divisor, pad_div;
-  int32_t init, fill;
-  hipStream_t st;
-};
-
-template <int N>
-SumArgs<N> sum_args(const SumCall& c, int n) {
-  SumArgs<N> a{};
-  for (int k = 0; k < n; ++k) { a.q[k] = c.q[k]; a.norm[k] = c.norm[k]; }
-  a.y = c.y; a.levels = c.levels; a.inv_levels = c.inv_levels; a.divisor = c.divisor; a.pad_div = c.pad_div;
-  a.init = c.init; a.fill = c.fill;
-  return a;
-}
-
-template <int W, bool P, int N>
-void launch_sum_n(const SumCall& c) {
-  const omf_plan* p = c.p;
-  const int64_t qlast = (p->arena_end & ~(int64_t)3) - 4;  // the last whole quad (as decode_blocks)
-  const int64_t per = kDecBlk / kSumBlk;                   // sum blocks per table block
-  hipLaunchKernelGGL((qsgd_decode_sum_arena<W, P, N>), dim3((unsigned)(p->n_dec_blocks * per)), dim3(kThreads), 0,
-                     c.st, sum_args<N>(c, N), (const uint32_t*)p->d_dec_binfo, (const int64_t*)p->d_begins,
-                     (const int64_t*)p->d_sizes, p->nt, qlast, p->arena_end);
-}
-
-template <int W, bool P>
-void launch_sum(const SumCall& c, int n) {
-  if (c.p->arena_end < 4) {  // no whole quad: the element kernel
-    hipLaunchKernelGGL((qsgd_decode_sum_tiny<W, P>), dim3(1), dim3(64), 0, c.st, sum_args<kSumMax>(c, n), n,
-                       (const int64_t*)c.p->d_begins, (const int64_t*)c.p->d_sizes, c.p->nt, c.p->arena_end);
-    return;
-  }
-  static_assert(kSumMax == 8, "one case per group size");
-  switch (n) {
-    case 1: launch_sum_n<W, P, 1>(c); break;
-    case 2: launch_sum_n<W, P, 2>(c); break;
-    case 3: launch_sum_n<W, P, 3>(c); break;
-    case 4: launch_sum_n<W, P, 4>(c); break;
-    case 5: launch_sum_n<W, P, 5>(c); break;
-    case 6: launch_sum_n<W, P, 6>(c); break;
-    case 7: launch_sum_n<W, P, 7>(c); break;
-    default: launch_sum_n<W, P, 8>(c); break;
-  }
-}
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
-
-extern "C" int omf_qsgd_decode_sum(omf_plan* p, const void* const* q, const float* const* norm, int32_t nclients,
-                                   int32_t width, int32_t levels, float* y, int32_t init, float divisor,
-                                   void* stream) {
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
-  if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
-  if (nclients < 1) return fail(OMF_EINVAL, "omf_qsgd_decode_sum: nclients must be >= 1");
-  if (!q || !norm || !y) return fail(OMF_EINVAL, "q, norm and y_out must be non-NULL");
-  if (!aligned(y, 16)) return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
-  const size_t ybytes = (size_t)p->arena_end * 4;
-  const size_t qbytes = width == 8 ? (size_t)((p->arena_end + 3) & ~(int64_t)3) : (size_t)p->arena_end * 4;
-  for (int32_t k = 0; k < nclients; ++k) {
-    if (!q[k] || !norm[k]) return fail(OMF_EINVAL, "omf_qsgd_decode_sum: a NULL entry in q or norm");
-    if (!aligned(q[k], width == 8 ? 4 : 16))
-      return fail(OMF_EINVAL, "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)");
-    if (overlaps(y, ybytes, q[k], qbytes) || overlaps(y, ybytes, norm[k], (size_t)p->nt * 4))
-      return fail(OMF_EINVAL, "omf_qsgd_decode_sum: y_out overlaps a payload or norm buffer");
-  }
-  DeviceGuard g(p->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  const bool pow2 = (levels & (levels - 1)) == 0;
-  SumCall c;
-  c.p = p; c.y = y; c.st = (hipStream_t)stream;
-  c.levels = (float)levels;
-  c.inv_levels = pow2 ? 1.0f / (float)levels : 0.0f;  // exact for a power of two
-  // Groups of at most kSumMax clients, chained: later groups start from y, the first fills the
-  // padding, the last divides.
-  for (int32_t k0 = 0; k0 < nclients; k0 += kSumMax) {
-    const int n = std::min<int32_t>(kSumMax, nclients - k0);
-    c.q = q + k0; c.norm = norm + k0;
-    c.init = (k0 > 0 || init) ? 1 : 0;
-    c.fill = (k0 == 0 && !init) ? 1 : 0;
-    c.divisor = k0 + n == nclients ? divisor : 0.0f;
-    c.pad_div = divisor;
-    if (width == 8) {
-      if (pow2) launch_sum<1, true>(c, n); else launch_sum<1, false>(c, n);
-    } else {
-      if (pow2) launch_sum<4, true>(c, n); else launch_sum<4, false>(c, n);
-    }
-    OMF_HIP(hipGetLastError());
-  }
-  return OMF_OK;
-}

@@ -37,6 +37,7 @@
 #include "omf_bracket.h"
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_qsgd_dec.h"
 #include "omf_qsgd_dev.h"
 #include "omf_qsgd_enc.h"
 
@@ -119,24 +120,19 @@ __device__ __forceinline__ int4 acc_load(const void* q, int64_t e, int64_t end) 
   return r;
 }
 
-// v + decode(raw): the decoder's arithmetic (qsgd_decode_arena with accumulate).
+// v + decode(raw): the decoders' element rule (qsgd_dec_elem, omf_qsgd_dec.h), as an accumulating decode.
 template <int AW>
 __device__ __forceinline__ float4 acc_add4(float4 v, int4 raw, float norm, float alevels, float ainv) {
   int32_t qi[4];
   if (AW == 1) {
-    qi[0] = (int32_t)(int8_t)(raw.x & 0xff);
-    qi[1] = (int32_t)(int8_t)((raw.x >> 8) & 0xff);
-    qi[2] = (int32_t)(int8_t)((raw.x >> 16) & 0xff);
-    qi[3] = (int32_t)(int8_t)((raw.x >> 24) & 0xff);
+    qsgd_split_i8(raw.x, qi);
   } else {
     qi[0] = raw.x; qi[1] = raw.y; qi[2] = raw.z; qi[3] = raw.w;
   }
   float y[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float nq = __fmul_rn(norm, (float)qi[c]);
-    y[c] = ainv != 0.0f ? __fmul_rn(nq, ainv) : nq / alevels;
-  }
+  for (int c = 0; c < 4; ++c)
+    y[c] = ainv != 0.0f ? qsgd_dec_elem<true>(norm, qi[c], alevels, ainv) : qsgd_dec_elem<false>(norm, qi[c], alevels, ainv);
   return make_float4(__fadd_rn(v.x, y[0]), __fadd_rn(v.y, y[1]), __fadd_rn(v.z, y[2]), __fadd_rn(v.w, y[3]));
 }
 

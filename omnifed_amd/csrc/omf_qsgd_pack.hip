@@ -9,15 +9,14 @@
 // offset_t * b / 32 (the offsets must be multiples of 32 elements, else OMF_EINVAL;
 // arena_layout's are multiples of 64), so 32 consecutive elements are exactly b words, lie in
 // one tensor, and one thread packs or unpacks them alone.
-// Decoding the codes gives the same floats as decoding the levels (qsgd_decode_flat's
-// arithmetic: fl32(fl32(norm * q) / L)).
-#include <algorithm>
+// Decoding the codes gives the same floats as decoding the levels: both wires decode an element with
+// qsgd_dec_elem and chain the sums' groups by sum_group (omf_qsgd_dec.h).
 #include <cstdint>
-#include <vector>
 
 #include "../../include/omf_codec.h"
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_qsgd_dec.h"
 
 using namespace omf;
 
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_pack(const void* __restrict__ q
 }
 
 // Decode over the arena, one workgroup per 8 Ki-element block (two blocks of the plan's 4 Ki
-// decoder table, omf_qsgd.hip qsgd_decode_arena): every lane's b packed words go out first, their
+// decoder table, omf_qsgd_recv.hip qsgd_decode_arena): every lane's b packed words go out first, their
 // addresses depending on blockIdx only, with the block's tensor and norm as scalar loads in
 // flight (the item-indexed version waited for its item and norm, then walked its item pass by
 // pass: 0.38 ms on Llama-400M).  Each thread unpacks its 32 elements into LDS; the workgroup
@@ -171,8 +170,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
     const int32_t qi = (int32_t)((uint32_t)(acc & mask) - (uint32_t)L);  // modulo 2^32 (b = 32: codes above INT32_MAX)
     acc >>= b;
     nb -= b;
-    const float nq = __fmul_rn(nrm, (float)qi);  // qsgd_decode_arena's arithmetic
-    tile[threadIdx.x * 33 + i] = POW2 ? __fmul_rn(nq, inv_levels) : nq / levels;
+    tile[threadIdx.x * 33 + i] = qsgd_dec_elem<POW2>(nrm, qi, levels, inv_levels);
   }
   __syncthreads();
 #pragma unroll
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
 
 // N clients' packed payloads decoded and summed in one pass (omf_qsgd_decode_sum_packed), in
 // qsgd_decode_packed's shape: one workgroup per 8 Ki-element block, one 32-element group per thread.
-//   s = init ? y : +0;  s = fl32(s + fl32(fl32(norm_c[t] * (code_c - L)) / levels))  c = 0..N-1;
+//   s = init ? y : +0;  s = fl32(s + qsgd_dec_elem(norm_c[t], code_c - L))  c = 0..N-1;
 //   y = divisor != 0 ? s / divisor : s
 // the bytes of omf_qsgd_decode_sum on the same levels unpacked.  All N clients' b words of the
 // thread's group go out first (unconditional, clamped to the packed arena's last group), with the
@@ -311,8 +309,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_sum_packed(PackedSumArgs
         code = (uint32_t)((two >> (bit & 31)) & mask);
       }
       const int32_t qi = (int32_t)(code - (uint32_t)a.L);
-      const float nq = __fmul_rn(nrm[c], (float)qi);  // qsgd_decode_arena's arithmetic
-      s[i] = __fadd_rn(s[i], POW2 ? __fmul_rn(nq, a.inv_levels) : nq / a.levels);
+      s[i] = __fadd_rn(s[i], qsgd_dec_elem<POW2>(nrm[c], qi, a.levels, a.inv_levels));
     }
     // One client at a time: the sums are pinned in their registers here.  Left free, the compiler sinks
     // every client's unpack and adds to the end and holds all their codes at once (256 VGPRs, one
@@ -359,115 +356,58 @@ struct ArenaArgs {
   int64_t arena_end;
 };
 
-template <int WIDTH, int B>
-void launch_pack(dim3 g, hipStream_t st, const void* q, const ArenaArgs& a, int32_t L, int32_t b, uint32_t* out) {
-  hipLaunchKernelGGL((qsgd_pack<WIDTH, B>), g, dim3(kThreads), 0, st, q, a.binfo, a.nbinfo, a.begins, a.sizes, a.nt,
-                     a.arena_end, L, b, out);
+// f(std::integral_constant<int, B>): B = b for the compile-time code widths 2..10, else 0 (the runtime width).
+template <class F>
+void with_code_bits(int b, F&& f) {
+  switch (b) {
+#define OMF_B(B) case B: f(std::integral_constant<int, B>{}); break;
+    OMF_B(2) OMF_B(3) OMF_B(4) OMF_B(5) OMF_B(6) OMF_B(7) OMF_B(8) OMF_B(9) OMF_B(10)
+#undef OMF_B
+    default: f(std::integral_constant<int, 0>{}); break;
+  }
 }
 
 template <int WIDTH>
 void dispatch_pack(int b, dim3 g, hipStream_t st, const void* q, const ArenaArgs& a, int32_t L, uint32_t* out) {
-  switch (b) {
-    case 2: launch_pack<WIDTH, 2>(g, st, q, a, L, b, out); break;
-    case 3: launch_pack<WIDTH, 3>(g, st, q, a, L, b, out); break;
-    case 4: launch_pack<WIDTH, 4>(g, st, q, a, L, b, out); break;
-    case 5: launch_pack<WIDTH, 5>(g, st, q, a, L, b, out); break;
-    case 6: launch_pack<WIDTH, 6>(g, st, q, a, L, b, out); break;
-    case 7: launch_pack<WIDTH, 7>(g, st, q, a, L, b, out); break;
-    case 8: launch_pack<WIDTH, 8>(g, st, q, a, L, b, out); break;
-    case 9: launch_pack<WIDTH, 9>(g, st, q, a, L, b, out); break;
-    case 10: launch_pack<WIDTH, 10>(g, st, q, a, L, b, out); break;
-    default: launch_pack<WIDTH, 0>(g, st, q, a, L, b, out); break;
-  }
+  with_code_bits(b, [&](auto B) {
+    hipLaunchKernelGGL((qsgd_pack<WIDTH, B()>), g, dim3(kThreads), 0, st, q, a.binfo, a.nbinfo, a.begins, a.sizes, a.nt,
+                       a.arena_end, L, b, out);
+  });
 }
 
 template <bool ACC, bool POW2>
 void dispatch_decode(int b, dim3 g, hipStream_t st, const uint32_t* packed, const ArenaArgs& a, const float* norm,
                      float* y, int32_t L, float levels, float inv) {
-#define OMF_DP(BB)                                                                                               \
-  hipLaunchKernelGGL((qsgd_decode_packed<BB, ACC, POW2>), g, dim3(kThreads), 0, st, packed, a.binfo, a.nbinfo, norm, \
-                     a.begins, a.sizes, a.nt, a.arena_end, y, L, b, levels, inv)
-  switch (b) {
-    case 2: OMF_DP(2); break;
-    case 3: OMF_DP(3); break;
-    case 4: OMF_DP(4); break;
-    case 5: OMF_DP(5); break;
-    case 6: OMF_DP(6); break;
-    case 7: OMF_DP(7); break;
-    case 8: OMF_DP(8); break;
-    case 9: OMF_DP(9); break;
-    case 10: OMF_DP(10); break;
-    default: OMF_DP(0); break;
-  }
-#undef OMF_DP
+  with_code_bits(b, [&](auto B) {
+    hipLaunchKernelGGL((qsgd_decode_packed<B(), ACC, POW2>), g, dim3(kThreads), 0, st, packed, a.binfo, a.nbinfo, norm,
+                       a.begins, a.sizes, a.nt, a.arena_end, y, L, b, levels, inv);
+  });
 }
 
 // ---- omf_qsgd_decode_sum_packed: one group of at most kPackedSumMax clients per launch
-struct PackedSumCall {
+struct PackedSumCall : SumCallBase {
   ArenaArgs a;
   dim3 grid;
   const uint32_t* const* packed;
-  const float* const* norm;
-  float* y;
-  float levels, inv_levels, divisor, pad_div;
-  int32_t init, fill, L, b;
-  hipStream_t st;
+  int32_t L, b;
 };
 
 template <int B, bool P, int N>
 void launch_psum_n(const PackedSumCall& c) {
   PackedSumArgs<N> k{};
-  for (int i = 0; i < N; ++i) { k.packed[i] = c.packed[i]; k.norm[i] = c.norm[i]; }
-  k.y = c.y; k.levels = c.levels; k.inv_levels = c.inv_levels; k.divisor = c.divisor; k.pad_div = c.pad_div;
-  k.init = c.init; k.fill = c.fill; k.L = c.L; k.b_rt = c.b;
+  for (int i = 0; i < N; ++i) k.packed[i] = c.packed[i];
+  sum_common_args(k, c, N);
+  k.L = c.L; k.b_rt = c.b;
   hipLaunchKernelGGL((qsgd_decode_sum_packed<B, P, N>), c.grid, dim3(kThreads), 0, c.st, k, c.a.binfo, c.a.nbinfo,
                      c.a.begins, c.a.sizes, c.a.nt, c.a.arena_end);
 }
 
-template <int B, bool P>
-void launch_psum(const PackedSumCall& c, int n) {
-  static_assert(kPackedSumMax == 8 && kPackedSumMaxWide == 4, "one case per group size");
-  if constexpr (B != 0) {
-    switch (n) {
-      case 5: launch_psum_n<B, P, 5>(c); return;
-      case 6: launch_psum_n<B, P, 6>(c); return;
-      case 7: launch_psum_n<B, P, 7>(c); return;
-      case 8: launch_psum_n<B, P, 8>(c); return;
-      default: break;
-    }
-  }
-  switch (n) {
-    case 1: launch_psum_n<B, P, 1>(c); break;
-    case 2: launch_psum_n<B, P, 2>(c); break;
-    case 3: launch_psum_n<B, P, 3>(c); break;
-    default: launch_psum_n<B, P, 4>(c); break;
-  }
-}
-
 template <bool P>
 void dispatch_psum(const PackedSumCall& c, int n) {
-  switch (c.b) {
-    case 2: launch_psum<2, P>(c, n); break;
-    case 3: launch_psum<3, P>(c, n); break;
-    case 4: launch_psum<4, P>(c, n); break;
-    case 5: launch_psum<5, P>(c, n); break;
-    case 6: launch_psum<6, P>(c, n); break;
-    case 7: launch_psum<7, P>(c, n); break;
-    case 8: launch_psum<8, P>(c, n); break;
-    case 9: launch_psum<9, P>(c, n); break;
-    case 10: launch_psum<10, P>(c, n); break;
-    default: launch_psum<0, P>(c, n); break;
-  }
+  with_code_bits(c.b, [&](auto B) {
+    with_group_size<(B() != 0 ? kPackedSumMax : kPackedSumMaxWide)>(n, [&](auto N) { launch_psum_n<B(), P, N()>(c); });
+  });
 }
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
-
-namespace {
 
 // The plan's arena for the packed wire, or an error: every tensor offset a multiple of 32
 // elements (a tensor's stream then starts on a word, and a 32-element group lies in one tensor).
@@ -504,7 +444,7 @@ int omf_qsgd_pack(omf_plan* plan, const void* q, int32_t width, int32_t levels, 
   if (width == 8 && levels > 127) return fail(OMF_EINVAL, "an int8 payload holds levels <= 127");
   if (!q || !packed) return fail(OMF_EINVAL, "q and packed must be non-NULL");
   // even widths store 8-byte word pairs: the packed arena must be 8-byte aligned
-  if (((uintptr_t)q & 15) || ((uintptr_t)packed & 7)) return fail(OMF_EINVAL, "q must be 16-byte, packed 8-byte aligned");
+  if (!aligned(q, 16) || !aligned(packed, 8)) return fail(OMF_EINVAL, "q must be 16-byte, packed 8-byte aligned");
   ArenaArgs a;
   dim3 grid;
   if (const int rc = packed_arena(plan, &a, &grid)) return rc;
@@ -523,20 +463,19 @@ int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t level
   const int32_t b = omf_qsgd_packed_bits(levels);
   if (b < 0 || b > 32) return fail(OMF_EINVAL, "levels must be in [1, 2^31 - 1)");
   if (!packed || !norm || !y) return fail(OMF_EINVAL, "packed, norm and y must be non-NULL");
-  if (((uintptr_t)y & 15) || ((uintptr_t)packed & 3)) return fail(OMF_EINVAL, "y must be 16-byte, packed 4-byte aligned");
+  if (!aligned(y, 16) || !aligned(packed, 4)) return fail(OMF_EINVAL, "y must be 16-byte, packed 4-byte aligned");
   ArenaArgs a;
   dim3 grid;
   if (const int rc = packed_arena(plan, &a, &grid)) return rc;
   DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   hipStream_t st = (hipStream_t)stream;
-  const bool pow2 = (levels & (levels - 1)) == 0;
-  const float lv = (float)levels, inv = pow2 ? 1.0f / (float)levels : 0.0f;
-#define OMF_DD(A, P) dispatch_decode<A, P>(b, grid, st, packed, a, norm, y, levels, lv, inv)
+  const LevelScale lv(levels);
+#define OMF_DD(A, P) dispatch_decode<A, P>(b, grid, st, packed, a, norm, y, levels, lv.levels, lv.inv_levels)
   if (accumulate) {
-    if (pow2) OMF_DD(true, true); else OMF_DD(true, false);
+    if (lv.pow2) OMF_DD(true, true); else OMF_DD(true, false);
   } else {
-    if (pow2) OMF_DD(false, true); else OMF_DD(false, false);
+    if (lv.pow2) OMF_DD(false, true); else OMF_DD(false, false);
   }
 #undef OMF_DD
   OMF_HIP(hipGetLastError());
@@ -550,34 +489,26 @@ int omf_qsgd_decode_sum_packed(omf_plan* plan, const uint32_t* const* packed, co
   const int32_t b = omf_qsgd_packed_bits(levels);
   if (b < 0 || b > 32) return fail(OMF_EINVAL, "levels must be in [1, 2^31 - 1)");
   if (!packed || !norm || !y) return fail(OMF_EINVAL, "packed, norm and y_out must be non-NULL");
-  if ((uintptr_t)y & 15) return fail(OMF_EINVAL, "y_out must be 16-byte aligned");
+  if (!aligned(y, 16)) return fail(OMF_EINVAL, "y_out must be 16-byte aligned");
   PackedSumCall c;
   if (const int rc = packed_arena(plan, &c.a, &c.grid)) return rc;
   const size_t ybytes = (size_t)plan->arena_end * 4;
   const size_t pbytes = (size_t)((plan->arena_end + 31) / 32) * (size_t)b * 4;
   for (int32_t k = 0; k < nclients; ++k) {
     if (!packed[k] || !norm[k]) return fail(OMF_EINVAL, "omf_qsgd_decode_sum_packed: a NULL entry in packed or norm");
-    if ((uintptr_t)packed[k] & 3) return fail(OMF_EINVAL, "a packed arena must be 4-byte aligned");
+    if (!aligned(packed[k], 4)) return fail(OMF_EINVAL, "a packed arena must be 4-byte aligned");
     if (overlaps(y, ybytes, packed[k], pbytes) || overlaps(y, ybytes, norm[k], (size_t)plan->nt * 4))
       return fail(OMF_EINVAL, "omf_qsgd_decode_sum_packed: y_out overlaps a packed or norm buffer");
   }
   DeviceGuard g(plan->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  const bool pow2 = (levels & (levels - 1)) == 0;
-  c.y = y; c.st = (hipStream_t)stream; c.L = levels; c.b = b;
-  c.levels = (float)levels;
-  c.inv_levels = pow2 ? 1.0f / (float)levels : 0.0f;  // exact for a power of two
-  // Groups of at most `per` clients, chained: later groups start from y, the first fills the
-  // padding, the last divides (omf_qsgd_decode_sum's rules).
+  const LevelScale lv(levels);
+  c.y = y; c.st = (hipStream_t)stream; c.L = levels; c.b = b; c.levels = lv.levels; c.inv_levels = lv.inv_levels;
   const int32_t per = b <= 10 ? kPackedSumMax : kPackedSumMaxWide;
-  for (int32_t k0 = 0; k0 < nclients; k0 += per) {
-    const int n = std::min<int32_t>(per, nclients - k0);
+  for (int32_t k0 = 0; k0 < nclients; k0 += per) {  // the chained groups (sum_group, omf_qsgd_dec.h)
+    c.g = sum_group(nclients, per, init, divisor, k0);
     c.packed = packed + k0; c.norm = norm + k0;
-    c.init = (k0 > 0 || init) ? 1 : 0;
-    c.fill = (k0 == 0 && !init) ? 1 : 0;
-    c.divisor = k0 + n == nclients ? divisor : 0.0f;
-    c.pad_div = divisor;
-    if (pow2) dispatch_psum<true>(c, n); else dispatch_psum<false>(c, n);
+    if (lv.pow2) dispatch_psum<true>(c, c.g.n); else dispatch_psum<false>(c, c.g.n);
     OMF_HIP(hipGetLastError());
   }
   return OMF_OK;

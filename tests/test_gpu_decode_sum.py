@@ -173,7 +173,7 @@ def test_non_finite_norms(arena, width, levels):
 # ------------------------------------------------------------------ 3. init=True
 
 @pytest.mark.parametrize("divisor", [None, 3.0])
-@pytest.mark.parametrize("K", [1, 8, 9])
+@pytest.mark.parametrize("K", [1, 8, 9, 17])  # 17 = 8 + 8 + 1: a middle group (from y, no fill, no division)
 @pytest.mark.parametrize("width,levels", [(8, 16), (8, 10), (32, 256), (32, 1000)])
 def test_init_extends_y_and_keeps_padding(arena, width, levels, K, divisor):
     cl = arena.clients(width, levels)
