@@ -64,7 +64,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 114
+#define OMF_ABI_VERSION 115
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -453,6 +453,37 @@ int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indic
  */
 int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64_t* indices, int32_t* flags,
                               void* stream);
+
+/*
+ * Opt-in bit-packed Top-K index wire ("TopKBitPackedCompression"; ours: the reference sends every
+ * index as an int64, global_grpc_compression.py:88-98, and cannot read this).  The k tensor-local
+ * indices of a tensor of n elements take b = omf_topk_index_bits(n) bits each, LSB-first
+ * little-endian, in the selection's order: index i at bits [i b, (i + 1) b) of the tensor's stream.
+ * In a plan's packed arena for the per-tensor counts k_t (0 <= k_t <= n_t, as omf_topk_decode_counts)
+ * tensor t's stream starts at word sum_{u<t} ceil(k_u / 32) b_u: 32 consecutive indices of a tensor
+ * are b whole words.
+ *
+ * omf_topk_index_bits (ours; host only): max(1, bit_length(n - 1)); -1 outside 1 <= n <= 2^32.
+ * omf_topk_packed_words (ours; host only, counts a HOST array): the arena's 32-bit words, or -1 on bad
+ *   counts or a tensor of more than 2^32 elements.
+ * omf_topk_pack_indices (replaces the .cpu() copy of the int64 indices in the sender,
+ *   global_grpc_compression.py:88-98): indices (int64, packed per tensor at sum_{u<t} k_u, each in
+ *   [0, n_t) — anything else is memory-safe and unspecified) -> packed; every word of the arena is
+ *   written, the codes after a tensor's k_t-th index as 0.
+ * omf_topk_unpack_indices (replaces np.frombuffer(indices_data, int64) + the host-to-device copy of the
+ *   receiver, global_grpc_compression.py:140-160): packed -> the first k_t indices of each tensor,
+ *   zero-extended; the bits past a tensor's k_t b are never used (a receiver's staging buffer is
+ *   uninitialised there).
+ * Both device calls are asynchronous on `stream`; sum k_t = 0 launches nothing.  OMF_EINVAL: a NULL
+ * pointer, packed not 4-byte or indices not 8-byte aligned, the two buffers overlapping, bad counts.
+ * The plan keeps the tables of the last 8 count vectors it saw (uploaded on first use).
+ */
+int32_t omf_topk_index_bits(int64_t n);
+int64_t omf_topk_packed_words(omf_plan* plan, const int64_t* counts);
+int omf_topk_pack_indices(omf_plan* plan, const int64_t* counts, const int64_t* indices, uint32_t* packed,
+                          void* stream);
+int omf_topk_unpack_indices(omf_plan* plan, const int64_t* counts, const uint32_t* packed, int64_t* indices,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,10 @@ SIGNATURES = {
                                               _c_p]),
     "omf_topk_check_indices": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
     "omf_topk_check_duplicates": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
+    "omf_topk_index_bits": (_c_i32, [_c_i64]),
+    "omf_topk_packed_words": (_c_i64, [_c_p, ctypes.POINTER(_c_i64)]),
+    "omf_topk_pack_indices": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
+    "omf_topk_unpack_indices": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
 }
 
 _lock = threading.Lock()
@@ -96,7 +100,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 114 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 115 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

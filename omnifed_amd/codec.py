@@ -45,6 +45,18 @@ def packed_bits(levels: int) -> int:
     return (2 * levels).bit_length()
 
 
+TOPK_INDEX_MAX_ELEMS = 2**32
+
+
+def topk_index_bits(numel: int) -> int:
+    """Bits per index of the opt-in packed Top-K wire: max(1, bit_length(numel - 1))
+    (omf_topk_index_bits); tensors of 1 to 2^32 elements."""
+    numel = int(numel)
+    if not 1 <= numel <= TOPK_INDEX_MAX_ELEMS:
+        raise ValueError(f"the packed Top-K wire takes tensors of 1 to 2^32 elements, not {numel}")
+    return max(1, (numel - 1).bit_length())
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -119,6 +131,7 @@ class Plan:
         self._dec_ws: Dict[int, torch.Tensor] = {}   # tiled Top-K decode workspace, per stream
         self._dec_need: Dict[float, int] = {}
         self._counts_cache: Dict[tuple, tuple] = {}
+        self._packed_cache: Dict[tuple, tuple] = {}
         self._topk_cache: Dict[float, tuple] = {}
         self.topk_reordered = 0  # tensors the latest tie_order="torch" encode rewrote (diagnostics)
         # the library's choice (by arena size, or OMF_ENCODE_STRATEGY)
@@ -741,6 +754,69 @@ class Plan:
                 self._dec_ws.pop(st, None)
             check(rc, "omf_topk_decode_counts")
         return y
+
+    # ------------------------------------------------------------ bit-packed Top-K indices (opt-in)
+    def topk_packed_layout(self, counts: Sequence[int]):
+        """``(bits, woff, words)`` of the packed index arena for the per-tensor ``counts``: tensor t's
+        indices in ``bits[t]`` bits each from 32-bit word ``woff[t]`` = Σ_{u<t} ceil(k_u / 32) · bits[u]
+        (a group of 32 indices is ``bits[t]`` whole words), ``words`` in all (omf_topk_packed_words)."""
+        key = tuple(int(c) for c in counts)
+        with self._lock:
+            got = self._packed_cache.get(key)
+        if got is None:
+            arr, _, _ = self._counts(key)
+            bits = [topk_index_bits(n) for n in self.sizes]
+            woff, cur = [], 0
+            for k, b in zip(key, bits):
+                woff.append(cur)
+                cur += -(-k // 32) * b
+            words = int(lib().omf_topk_packed_words(self._h, arr))
+            if words != cur:
+                raise CodecError(f"omf_topk_packed_words: {words} words, the layout rule gives {cur}")
+            got = (bits, woff, words)
+            with self._lock:
+                while len(self._packed_cache) >= 16:
+                    self._packed_cache.pop(next(iter(self._packed_cache)))
+                self._packed_cache[key] = got
+        return got
+
+    def topk_packed_words(self, counts: Sequence[int]) -> int:
+        return self.topk_packed_layout(counts)[2]
+
+    def topk_pack_indices(self, counts: Sequence[int], indices: torch.Tensor,
+                          packed_out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_topk_pack_indices: the int64 ``indices`` of a selection (``counts[t]`` per tensor, packed in
+        plan order, each in [0, n_t)) into the packed index arena (an int32 tensor of
+        ``topk_packed_words(counts)`` words).  Asynchronous."""
+        arr, ktot, _ = self._counts(counts)
+        words = self.topk_packed_words(counts)
+        dev = self.device
+        _need(indices, "indices", torch.int64, dev, ktot, 8)
+        if packed_out is None:
+            packed_out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+        _need(packed_out, "packed_out", torch.int32, dev, words, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_topk_pack_indices(self._h, arr, _ptr(indices), _ptr(packed_out), ctypes.c_void_p(st)),
+                  "omf_topk_pack_indices")
+        return packed_out
+
+    def topk_unpack_indices(self, counts: Sequence[int], packed: torch.Tensor,
+                            indices_out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_topk_unpack_indices: the packed index arena back into int64 indices (``counts[t]`` per
+        tensor, packed in plan order); the bits past a tensor's last index are not used.  Asynchronous."""
+        arr, ktot, _ = self._counts(counts)
+        words = self.topk_packed_words(counts)
+        dev = self.device
+        _need(packed, "packed", torch.int32, dev, words, 4)
+        if indices_out is None:
+            indices_out = torch.empty(max(ktot, 1), dtype=torch.int64, device=dev)
+        _need(indices_out, "indices_out", torch.int64, dev, ktot, 8)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_topk_unpack_indices(self._h, arr, _ptr(packed), _ptr(indices_out), ctypes.c_void_p(st)),
+                  "omf_topk_unpack_indices")
+        return indices_out
 
 
 def div_(y: torch.Tensor, divisor: float, stream: Optional[int] = None) -> torch.Tensor:

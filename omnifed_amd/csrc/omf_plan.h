@@ -187,16 +187,18 @@ inline void* topk_table(omf_plan* p, uint64_t key, size_t bytes, bool* fresh, ui
   return d;
 }
 // The same for tables keyed by an explicit per-tensor count vector (a received Top-K message's
-// k_t): matched on the exact counts.  At most kMaxCountTables are kept; making one more frees the
-// oldest (hipFree waits for the device, so no queued launch still reads it).
-inline void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes, bool* fresh, uint64_t** host) {
-  constexpr uint64_t kCountsKey = 0xC0C0C0C0C0C0C0C0ull;
+// k_t): matched on the kind and the exact counts.  At most kMaxCountTables of a kind are kept; making
+// one more frees the oldest (hipFree waits for the device, so no queued launch still reads it).
+constexpr uint64_t kCountsKey = 0xC0C0C0C0C0C0C0C0ull;      // the decode tables of a count vector
+constexpr uint64_t kPackCountsKey = 0xC0C0C0C0C0C0B175ull;  // its packed-index tables (kept 8 of each kind)
+inline void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes, bool* fresh, uint64_t** host,
+                               uint64_t kind = kCountsKey) {
   constexpr int kMaxCountTables = 8;
   *fresh = false;
   const size_t nt = (size_t)p->nt;
   int held = 0;
   for (auto& e : p->topk_tables) {
-    if (e.key != kCountsKey) continue;
+    if (e.key != kind) continue;
     ++held;
     if (e.counts.size() == nt && std::equal(e.counts.begin(), e.counts.end(), counts)) {
       *host = &e.host;
@@ -205,7 +207,7 @@ inline void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes,
   }
   if (held >= kMaxCountTables) {
     for (auto it = p->topk_tables.begin(); it != p->topk_tables.end(); ++it)
-      if (it->key == kCountsKey) {
+      if (it->key == kind) {
         (void)hipFree(it->dev);
         p->topk_tables.erase(it);
         break;
@@ -213,10 +215,13 @@ inline void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes,
   }
   void* d = nullptr;
   if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-  p->topk_tables.push_back({kCountsKey, d, 0, std::vector<int64_t>(counts, counts + nt)});
+  p->topk_tables.push_back({kind, d, 0, std::vector<int64_t>(counts, counts + nt)});
   *host = &p->topk_tables.back().host;
   *fresh = true;
   return d;
 }
+
+// 0 <= counts[t] <= sizes[t] for every tensor, *ktot their sum; else OMF_EINVAL (omf_topk_recv.hip).
+int topk_check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot);
 
 }  // namespace omf

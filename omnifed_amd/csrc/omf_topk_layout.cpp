@@ -200,5 +200,35 @@ Carve<DecWs> dec_ws_layout(int32_t nsuper, uint64_t cap_total, int64_t ktot) {
   return c;
 }
 
+PackTables pack_tables_host(const std::vector<int64_t>& sizes, const int64_t* ks) {
+  const size_t nt = sizes.size();
+  PackTables p;
+  p.bits.resize(nt);
+  p.koff.assign(nt + 1, 0);
+  p.goff.assign(nt + 1, 0);
+  p.woff.assign(nt + 1, 0);
+  bool ok = true;
+  for (size_t t = 0; t < nt; ++t) {
+    const int32_t b = index_bits(sizes[t]);
+    const int64_t groups = (ks[t] + kPackGroup - 1) / kPackGroup;
+    p.bits[t] = b;
+    p.koff[t + 1] = p.koff[t] + ks[t];
+    p.goff[t + 1] = p.goff[t] + groups;
+    p.woff[t + 1] = p.woff[t] + (b > 0 ? groups * b : 0);
+    ok = ok && b > 0;
+  }
+  p.words = ok ? p.woff[nt] : -1;
+  return p;
+}
+
+Carve<PackTable> pack_table_carve(int32_t nt) {
+  Carve<PackTable> c;
+  OMF_REGION(c, PackTable, koff, (size_t)nt + 1);
+  OMF_REGION(c, PackTable, woff, (size_t)nt + 1);
+  OMF_REGION(c, PackTable, goff, (size_t)nt + 1);
+  OMF_REGION(c, PackTable, bits, (size_t)nt);
+  return c;
+}
+
 }  // namespace topk_layout
 }  // namespace omf

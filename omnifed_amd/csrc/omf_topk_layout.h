@@ -1,7 +1,9 @@
 // omf_topk_layout.h — the host-only side of Top-K: the constants host and kernels share, the
 // per-tensor rules (k, bucket slots, sampling stride / runs / blocks, items, super-items) written
 // once for both, the encoder's constant tables and pipeline groups, the carve of the encode and
-// decode workspaces and of the plan-owned device tables, and the decoder's tables.
+// decode workspaces and of the plan-owned device tables, the decoder's tables, and the opt-in
+// bit-packed index wire (its width rule, the group pack / unpack the kernels and the host check share,
+// the packed arena's tables).
 //
 // Pure integer code: no HIP header, so tests/host/topk_layout_check.cpp runs it on a CPU under
 // sanitizers.  omf_topk.hip (the encoder) and omf_topk_recv.hip (decode and checks) upload what the
@@ -246,6 +248,85 @@ struct DecWs {
   uint64_t *pairs, *ovf;
 };
 Carve<DecWs> dec_ws_layout(int32_t nsuper, uint64_t cap_total, int64_t ktot);
+
+// ---------------------------------------------------------------- bit-packed indices (opt-in wire)
+// "TopKBitPackedCompression": the k tensor-local indices of a tensor of n elements in
+// b = index_bits(n) bits each, LSB-first little-endian — index i at bits [i b, (i + 1) b) of the tensor's
+// stream.  In a packed arena 32 consecutive indices of one tensor (a group; a tensor's last one may be
+// partial) are exactly b words and start on a word; tensor t's first group is goff[t], its first word woff[t].
+constexpr int kPackGroup = 32;
+constexpr int64_t kPackMaxElems = (int64_t)1 << 32;  // b <= 32
+
+// b = max(1, bit_length(n - 1)); -1 outside [1, 2^32].
+OMF_HD int32_t index_bits(int64_t n) {
+  if (n < 1 || n > kPackMaxElems) return -1;
+  int32_t b = 1;
+  while (b < 32 && ((int64_t)1 << b) < n) ++b;
+  return b;
+}
+
+// One group: the low b bits of idx[0, nv) and code 0 for the rest of the 32, into the b words out[0, b).
+OMF_HD void pack_group(const int64_t* idx, int nv, int b, uint32_t* out) {
+  const uint64_t mask = (1ull << b) - 1ull;
+  uint64_t acc = 0;
+  int nb = 0, w = 0;
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int i = 0; i < kPackGroup; ++i) {
+    const uint64_t code = i < nv ? (uint64_t)idx[i] & mask : 0ull;
+    acc |= code << nb;  // nb < 32 and code < 2^32: no bit is lost
+    nb += b;
+    if (nb >= 32) {
+      out[w++] = (uint32_t)acc;
+      acc >>= 32;
+      nb -= 32;
+    }
+  }
+}
+
+// The first nv codes of a group's words w[0, b), zero-extended into out[0, nv).  Only the words that
+// hold one of those codes are read, and of the last of them only the codes' bits are used: whatever
+// lies past bit nv * b does not matter.
+template <class T>
+OMF_HD void unpack_group(const uint32_t* w, int nv, int b, T* out) {
+  const uint64_t mask = (1ull << b) - 1ull;
+  uint64_t acc = 0;
+  int nb = 0, wi = 0;
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int i = 0; i < kPackGroup; ++i) {
+    if (i < nv) {
+      if (nb < b) {
+        acc |= (uint64_t)w[wi++] << nb;
+        nb += 32;
+      }
+      out[i] = (T)(acc & mask);
+      acc >>= b;
+      nb -= b;
+    }
+  }
+}
+
+// The packed arena of the selection layout ks over `sizes`: per tensor its width, first group
+// goff[t] = sum_{u<t} ceil(k_u / 32) and first word woff[t] = sum_{u<t} ceil(k_u / 32) b_u (both with
+// their totals at index nt), koff as the decode tables'.  words = woff[nt], or -1 when a tensor is
+// outside index_bits' range (its bits entry is -1 and it adds no words).
+struct PackTables {
+  std::vector<int32_t> bits;
+  std::vector<int64_t> koff, goff, woff;
+  int64_t words = 0;
+};
+PackTables pack_tables_host(const std::vector<int64_t>& sizes, const int64_t* ks);
+
+// The plan-owned device table of one PackTables (goff as 32-bit words: the callers refuse 2^32 groups).
+struct PackTable {
+  int64_t *koff, *woff;
+  uint32_t* goff;
+  int32_t* bits;
+};
+Carve<PackTable> pack_table_carve(int32_t nt);
 
 }  // namespace topk_layout
 }  // namespace omf

@@ -350,9 +350,12 @@ bool ratio_counts(const omf_plan* plan, double ratio, std::vector<int64_t>& ks, 
   return true;
 }
 
+}  // namespace
+
 // Explicit counts: 0 <= counts[t] <= n_t (a received selection of more values than its tensor
-// has elements would need duplicates; the caller decodes such a layer on its own).
-int check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot) {
+// has elements would need duplicates; the caller decodes such a layer on its own).  Shared with
+// omf_topk_pack.hip (declared in omf_plan.h).
+int omf::topk_check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot) {
   if (!counts) return fail(OMF_EINVAL, "counts is NULL");
   const std::vector<int64_t>& sizes = plan->sizes;
   int64_t s = 0;
@@ -364,6 +367,8 @@ int check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot) {
   *ktot = s;
   return OMF_OK;
 }
+
+namespace {
 
 uint64_t ratio_key(double ratio) {
   uint64_t k;
@@ -475,7 +480,7 @@ int omf_topk_decode_arena_ws(omf_plan* plan, double ratio, const float* values, 
 size_t omf_topk_decode_counts_workspace_bytes(const omf_plan* plan, const int64_t* counts) {
   if (!plan || !counts) return 0;
   int64_t ktot = 0;
-  if (check_counts(plan, counts, &ktot)) return 0;
+  if (topk_check_counts(plan, counts, &ktot)) return 0;
   return dec_ws_bytes(plan, counts, ktot);
 }
 
@@ -483,7 +488,7 @@ int omf_topk_decode_counts(omf_plan* plan, const int64_t* counts, const float* v
                            int32_t mode, void* ws, size_t ws_bytes, void* stream) {
   if (!plan) return fail(OMF_EINVAL, "plan is NULL");
   int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
+  if (int r = topk_check_counts(plan, counts, &ktot)) return r;
   return decode_layout(plan, counts, ktot, nullptr, values, indices, y, mode, ws, ws_bytes, stream);
 }
 
@@ -491,7 +496,7 @@ int omf_topk_check_indices(omf_plan* plan, const int64_t* counts, int64_t* indic
   if (!plan) return fail(OMF_EINVAL, "plan is NULL");
   if (!bad) return fail(OMF_EINVAL, "omf_topk_check_indices: bad is NULL");
   int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
+  if (int r = topk_check_counts(plan, counts, &ktot)) return r;
   if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_indices: indices is NULL");
   const int32_t nt = plan->nt;
   if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_indices: too many tensors");
@@ -514,7 +519,7 @@ int omf_topk_check_duplicates(omf_plan* plan, const int64_t* counts, const int64
   if (!plan) return fail(OMF_EINVAL, "plan is NULL");
   if (!flags) return fail(OMF_EINVAL, "omf_topk_check_duplicates: flags is NULL");
   int64_t ktot = 0;
-  if (int r = check_counts(plan, counts, &ktot)) return r;
+  if (int r = topk_check_counts(plan, counts, &ktot)) return r;
   if (ktot && !indices) return fail(OMF_EINVAL, "omf_topk_check_duplicates: indices is NULL");
   const int32_t nt = plan->nt;
   if (nt > kArenaMaxTensors) return fail(OMF_EINVAL, "omf_topk_check_duplicates: too many tensors");

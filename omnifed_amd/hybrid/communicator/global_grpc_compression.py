@@ -41,7 +41,8 @@ from ..compression.qsgd import (
     choose_qsgd_storage_width,
     should_compress_tensor,
 )
-from ..compression.topk import TOPK_COMPRESSION_NAME, TopKCompression, topk_index_offset
+from ..compression.topk import (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TopKCompression,
+                                topk_index_offset)
 from ..compression.core import compute_device
 from ... import codec, hostio
 
@@ -50,6 +51,7 @@ GlobalHybridCompressor = Union[TopKCompression, QSGDQuantCompression]
 _QSGD_NUMPY_DTYPES = {8: np.int8, 32: np.int32}
 _QSGD_TORCH_DTYPES = {8: torch.int8, 32: torch.int32}
 _QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME)
+_TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME)
 
 
 _STAGING = hostio.STAGING
@@ -87,13 +89,15 @@ def compression_mode_name(compressor: Optional[GlobalHybridCompressor]) -> str:
 
 def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_ratio: float = 0.01,
                             bit_width: int = 8, device="cpu", packed_wire: bool = False) -> Optional[GlobalHybridCompressor]:
-    """global_grpc_compression.py:35-52.  ``packed_wire`` (QSGD only, default off): the opt-in
-    bit-packed wire (``QSGDBitPackedCompression``, not readable by the reference)."""
+    """global_grpc_compression.py:35-52.  ``packed_wire`` (default off): the scheme's opt-in bit-packed
+    wire — ``QSGDBitPackedCompression`` (the levels in ceil(log2(2L + 1)) bits) or
+    ``TopKBitPackedCompression`` (the indices in max(1, bit_length(n - 1)) bits); neither is readable
+    by the reference."""
     if not enabled:
         return None
     scheme_norm = str(scheme).lower()
     if scheme_norm == "topk":
-        return TopKCompression(device=device, compress_ratio=float(compress_ratio))
+        return TopKCompression(device=device, compress_ratio=float(compress_ratio), packed_wire=bool(packed_wire))
     if scheme_norm == "qsgd":
         return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire))
     raise ValueError(f"Unsupported global_compression.scheme={scheme!r}; expected 'topk' or 'qsgd'")
@@ -199,6 +203,22 @@ def topk_layer_from_bytes(name: str, shape, values: bytes, indices: bytes):
     return layer
 
 
+def topk_packed_layer_from_bytes(name: str, shape, values: bytes, packed: bytes):
+    """The opt-in bit-packed Top-K ``LayerState``: the Top-K layer's values (fp32, the selection's order) and
+    ``indices_data`` = the k tensor-local indices in ``width`` = max(1, bit_length(n - 1)) bits each, LSB
+    first, the first ceil(k * width / 8) bytes of the stream."""
+    bits = codec.topk_index_bits(int(np.prod(tuple(shape))))
+    layer = global_grpc_pb2.layer_state(layer_name=name)
+    layer.compression_type = TOPK_PACKED_COMPRESSION_NAME
+    layer.values_data = values
+    layer.indices_data = packed
+    layer.values_dtype = "torch.float32"
+    layer.indices_dtype = f"packed.u{bits}"
+    layer.original_shape.extend(list(shape))
+    layer.width = bits
+    return layer
+
+
 def _weighted(tensor: torch.Tensor, weight) -> torch.Tensor:
     """``torch.mul(tensor, batch_samples)`` of GrpcCommunicator.aggregate (global_grpc.py:104, 121)."""
     return tensor if weight is None else torch.mul(tensor.detach(), weight)
@@ -209,7 +229,18 @@ def _alpha(weight) -> float:
 
 
 def _encode_topk_layer(name: str, tensor: torch.Tensor, compressor: TopKCompression, weight=None):
+    if compressor.packed_wire and _topk_batchable([tensor]):
+        return _encode_topk_updates({name: tensor}, compressor, weight)[0]  # a one-tensor plan, packed on the device
     (values, indices), _ctx = compressor.compress_weighted(tensor.detach(), name, _alpha(weight))
+    if compressor.packed_wire:  # (a bf16 tensor fails in .numpy() as on the plain wire)
+        vals = np.ascontiguousarray(values.detach().cpu().numpy(), dtype=np.float32).tobytes()
+        n, k = tensor.numel(), indices.numel()
+        dev = compute_device(tensor, compressor.device)
+        plan = codec.Plan.get([n], device=dev)
+        words = plan.topk_pack_indices([k], indices.detach().to(dev, torch.int64).contiguous())
+        nbytes = (k * codec.topk_index_bits(n) + 7) // 8
+        return topk_packed_layer_from_bytes(name, tuple(tensor.shape), vals,
+                                            words.cpu().numpy().tobytes()[:nbytes])
     return topk_layer_from_payload(name, tuple(tensor.shape), values.detach().cpu().numpy(),
                                    indices.detach().cpu().numpy())
 
@@ -268,17 +299,38 @@ def _last_wins(v: torch.Tensor, ix: torch.Tensor, n: int):
     return v[keep], ix[keep]
 
 
+def _unpack_topk_indices(packed: bytes, k: int, numel: int, dev: torch.device) -> np.ndarray:
+    """The k int64 indices of a packed layer's ``indices_data`` (checked by read_topk_layer): a one-tensor
+    unpack on the GPU.  A layer with more values than elements (malformed: it must repeat an index) is
+    outside the plan tables' count rule (k <= n); its few bits are unpacked with numpy."""
+    b = codec.topk_index_bits(numel)
+    if k > numel:
+        bits = np.unpackbits(np.frombuffer(packed, dtype=np.uint8), bitorder="little")[:k * b].reshape(k, b)
+        return (bits.astype(np.uint64) << np.arange(b, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64).astype(np.int64)
+    plan = codec.Plan.get([numel], device=dev)
+    words = plan.topk_packed_words([k])
+    raw = np.zeros(4 * words, dtype=np.uint8)
+    raw[:len(packed)] = np.frombuffer(packed, dtype=np.uint8)
+    return plan.topk_unpack_indices([k], torch.from_numpy(raw.view(np.int32)).to(dev))[:k].cpu().numpy()
+
+
 def _decode_topk_layer(layer, *, base_tensor: Optional[torch.Tensor] = None, device=None,
                        last_wins: bool = False) -> torch.Tensor:
     """global_grpc_compression.py:140-160: overlay on ``base_tensor`` or zero-filled dense.
     ``last_wins``: the layer repeats an index (omf_topk_check_duplicates): numpy's rule, the last
     value per index (always applied when there are more values than elements)."""
-    if not layer.values_data or not layer.indices_data:
-        raise ValueError(f"Compressed layer {layer.layer_name!r} missing values/indices")
-    values = np.frombuffer(layer.values_data, dtype=np.float32)
-    indices = np.frombuffer(layer.indices_data, dtype=np.int64)
     original_shape = tuple(layer.original_shape)
     numel = int(np.prod(original_shape))
+    if layer.compression_type == TOPK_PACKED_COMPRESSION_NAME:
+        # the packed wire: back to the int64 indices the plain wire carries, then the plain layer's code
+        vbytes, packed, k = read_topk_layer(layer)
+        values = np.frombuffer(vbytes, dtype=np.float32)
+        indices = _unpack_topk_indices(packed, k, numel, _gpu_for(_out_device(base_tensor, device)))
+    else:
+        if not layer.values_data or not layer.indices_data:
+            raise ValueError(f"Compressed layer {layer.layer_name!r} missing values/indices")
+        values = np.frombuffer(layer.values_data, dtype=np.float32)
+        indices = np.frombuffer(layer.indices_data, dtype=np.int64)
     if values.shape[0] != indices.shape[0]:
         raise ValueError(f"Compressed layer {layer.layer_name!r}: {values.shape[0]} values, {indices.shape[0]} indices")
     if indices.size and (indices.min() < -numel or indices.max() >= numel):
@@ -409,7 +461,7 @@ def decode_layer_tensor(layer, *, base_tensor: Optional[torch.Tensor] = None, de
         arr = np.array(layer.param_update, dtype=np.float32).reshape(tuple(layer.param_shape))
         out = torch.from_numpy(arr.copy())
         return out if device is None else out.to(device)
-    if compression_type == TOPK_COMPRESSION_NAME:
+    if compression_type in _TOPK_TYPES:
         return _decode_topk_layer(layer, base_tensor=base_tensor, device=device)
     if compression_type in _QSGD_TYPES:
         return _decode_qsgd_layer(layer, device=device)
@@ -471,6 +523,8 @@ def _encode_topk_updates(updates, compressor: TopKCompression, weight) -> list:
     koff = [0]
     for k in ks:
         koff.append(koff[-1] + k)
+    if compressor.packed_wire:
+        return _packed_topk_layers(plan, values, indices, ks, koff, names, updates, compressor)
     io = topk_index_offset(koff[-1])
     spans = [(4 * koff[t], 4 * ks[t]) for t in range(nt)] + [(io + 8 * koff[t], 8 * ks[t]) for t in range(nt)]
     buf = values.untyped_storage()
@@ -486,6 +540,26 @@ def _encode_topk_updates(updates, compressor: TopKCompression, weight) -> list:
             layers[t] = topk_layer_from_bytes(names[t], tuple(updates[names[t]].shape), vals[t], payload)
             vals[t] = None
     if compressor.tie_order != "torch":  # (torch order checked the plan already) an exact-tail expiry raises
+        plan.check()
+    return layers
+
+
+def _packed_topk_layers(plan, values, indices, ks, koff, names, updates, compressor) -> list:
+    """The opt-in packed wire of an encoded arena: ONE ``topk_pack_indices`` on the device, then the values
+    and the packed words device to host (hostio.device_to_bytes) — tensor t's index bytes are the first
+    ceil(k_t b_t / 8) of its stream at word woff[t]; the int64 indices never cross PCIe."""
+    nt = len(names)
+    bits, woff, _ = plan.topk_packed_layout(ks)  # ValueError for a tensor above 2^32 elements
+    words = plan.topk_pack_indices(ks, indices)
+    vals: List[Optional[bytes]] = [None] * nt
+    for t, payload in hostio.device_to_bytes(values, [(4 * koff[t], 4 * ks[t]) for t in range(nt)], key="topk_encode"):
+        vals[t] = payload
+    layers: List = [None] * nt
+    spans = [(4 * woff[t], (ks[t] * bits[t] + 7) // 8) for t in range(nt)]
+    for t, payload in hostio.device_to_bytes(words, spans, key="topk_encode_idx"):
+        layers[t] = topk_packed_layer_from_bytes(names[t], tuple(updates[names[t]].shape), vals[t], payload)
+        vals[t] = None
+    if compressor.tie_order != "torch":
         plan.check()
     return layers
 
@@ -648,6 +722,29 @@ def _decode_qsgd_to_host(layers, dev: torch.device):
     return out, plan
 
 
+def _read_packed_topk(layer, v: bytes, i: bytes):
+    """read_topk_layer for the opt-in packed wire: ``(values bytes, packed index bytes, k)`` once the
+    fields agree with the layer's own shape — width and indices_dtype are max(1, bit_length(n - 1)) and
+    ``indices_data`` is exactly ceil(k * width / 8) bytes."""
+    name = layer.layer_name
+    if len(v) % 4:
+        raise ValueError(f"Compressed layer {name!r}: buffer size must be a multiple of element size")
+    k, n = len(v) // 4, _layer_numel(layer)
+    try:
+        b = codec.topk_index_bits(n)
+    except ValueError:
+        raise ValueError(f"Compressed layer {name!r}: packed indices need 1 to 2^32 elements, shape has {n}") from None
+    if layer.width != b:
+        raise ValueError(f"Compressed layer {name!r} has unsupported width={layer.width} (expected {b} for {n} elements)")
+    if layer.indices_dtype != f"packed.u{b}":
+        raise ValueError(f"Compressed layer {name!r} has unsupported indices_dtype={layer.indices_dtype!r} "
+                         f"(expected 'packed.u{b}')")
+    if len(i) != (k * b + 7) // 8:
+        raise ValueError(f"Compressed layer {name!r}: {len(i)} index bytes, expected {(k * b + 7) // 8} "
+                         f"for {k} values of {b} bits")
+    return v, i, k
+
+
 def read_topk_layer(layer):
     """The Top-K layer's payloads, checked as the reference's decoder checks them before any
     work (global_grpc_compression.py:145-146; np.frombuffer raises ValueError on a size that is
@@ -657,6 +754,8 @@ def read_topk_layer(layer):
     i = layer.indices_data
     if not v or not i:
         raise ValueError(f"Compressed layer {layer.layer_name!r} missing values/indices")
+    if layer.compression_type == TOPK_PACKED_COMPRESSION_NAME:
+        return _read_packed_topk(layer, v, i)
     if len(v) % 4 or len(i) % 8:
         raise ValueError(f"Compressed layer {layer.layer_name!r}: buffer size must be a multiple of element size")
     if len(v) // 4 != len(i) // 8:
@@ -672,7 +771,7 @@ def _validate_layer(layer):
     if ct == "":
         if not layer.param_shape:
             raise ValueError(f"Dense layer {layer.layer_name!r} missing param_shape")
-    elif ct == TOPK_COMPRESSION_NAME:
+    elif ct in _TOPK_TYPES:
         return read_topk_layer(layer)
     elif ct == QSGD_COMPRESSION_NAME:
         _check_qsgd_fields(layer)  # the payload's size: checked as it is staged (_decode_qsgd_batch)
@@ -713,18 +812,37 @@ def _topk_batch_ok(topk) -> bool:
     return True
 
 
-def stage_topk(pairs, dev: torch.device, key: str):
+def stage_topk(pairs, dev: torch.device, key: str, packed_plan=None):
     """One device buffer holding a message's Top-K selections in plan order — values (fp32) at
     its start, indices (int64) from ``topk_index_offset(K)`` — through pinned staging in chunks
     (hostio.bytes_to_device).  ``pairs``: ``[(values bytes, indices bytes)]`` per plan tensor
     (``(b"", b"")`` for a tensor absent from the message).  Returns ``(counts, values, indices)``
-    (stream-ordered)."""
+    (stream-ordered).
+
+    ``packed_plan``: the message is on the opt-in packed wire and this is its plan (every count at most
+    its tensor's size).  The index bytes are then each layer's packed ``indices_data``, staged into a packed
+    region behind the int64 region — tensor t's at byte 4 * woff[t]; what follows its bytes in its last
+    group stays uninitialised — and ``topk_unpack_indices`` fills the int64 region on the device: 4 k + about
+    3 k bytes cross PCIe instead of 12 k.  From there on the message is a plain one."""
     counts = [len(v) // 4 for v, _ in pairs]
     koff = [0]
     for k in counts:
         koff.append(koff[-1] + k)
     K = koff[-1]
     io = topk_index_offset(K)
+    if packed_plan is not None:
+        _, woff, words = packed_plan.topk_packed_layout(counts)
+        po = (io + 8 * K + 255) // 256 * 256  # the packed region: past the int64 one
+        buf = torch.empty(max(po + 4 * words, 256), dtype=torch.uint8, device=dev)
+        items = [(4 * koff[t], (lambda v=v: v)) for t, (v, _) in enumerate(pairs)]
+        hostio.bytes_to_device(items, buf, 4 * K, key=key)
+        region = buf[po:po + 4 * words]
+        items = [(4 * woff[t], (lambda i=i: i)) for t, (_, i) in enumerate(pairs)]
+        hostio.bytes_to_device(items, region, 4 * words, key=key + "_idx")
+        indices = buf[io:io + 8 * K].view(torch.int64)
+        if K:
+            packed_plan.topk_unpack_indices(counts, region.view(torch.int32), indices_out=indices)
+        return counts, buf[:4 * K].view(torch.float32), indices
     buf = torch.empty(max(io + 8 * K, 256), dtype=torch.uint8, device=dev)
     items = [(4 * koff[t], (lambda v=v: v)) for t, (v, _) in enumerate(pairs)]
     items += [(io + 8 * koff[t], (lambda i=i: i)) for t, (_, i) in enumerate(pairs)]
@@ -740,13 +858,15 @@ def check_topk_indices(plan, counts, indices, names) -> None:
         raise IndexError(f"Compressed layer {names[bad]!r}: index out of bounds for size {plan.sizes[bad]}")
 
 
-def _decode_topk_batch(topk, dev: torch.device):
+def _decode_topk_batch(topk, dev: torch.device, packed: bool = False):
     """Decode a message's Top-K layers (zero-filled, no base) in one call: returns the decoded
     fp32 arena and the plan (layer t at ``[plan.offsets[t], + plan.sizes[t])``).  A layer that
     repeats an index is decoded again by itself with numpy's last-value rule (never for a
-    selection an encoder produced)."""
+    selection an encoder produced).  ``packed``: the layers are on the opt-in packed wire (stage_topk
+    unpacks their indices on the device; the rest is the same)."""
     plan = codec.Plan.get([_layer_numel(L) for L, *_ in topk], device=dev)
-    counts, values, indices = stage_topk([(v, i) for _L, v, i, _k in topk], dev, "topk_decode")
+    counts, values, indices = stage_topk([(v, i) for _L, v, i, _k in topk], dev, "topk_decode",
+                                         packed_plan=plan if packed else None)
     bad = plan.topk_check_indices(counts, indices)
     dup = plan.topk_check_duplicates(counts, indices)
     y = plan.topk_decode_counts(counts, values, indices, mode=0)  # out-of-range indices are skipped
@@ -783,17 +903,21 @@ def decode_updates_dict(proto_layers, *, base_updates: Optional[Dict[str, torch.
                 decoded[L.layer_name] = y[o:o + n].view(tuple(L.original_shape))
     if base_updates is not None:  # overlays decode layer by layer, on their bases' devices
         topk = [e for e in topk if e[0].layer_name not in base_updates]
-    if topk and _topk_batch_ok(topk):
-        y, plan = _decode_topk_batch(topk, _gpu_for(out_dev))
-        if out_dev.type == "cpu":
-            y = hostio.device_to_host(y, pool_memory=_HOST_POLICY)
-        for (L, *_), o, n in zip(topk, plan.offsets, plan.sizes):
-            decoded[L.layer_name] = y[o:o + n].view(tuple(L.original_shape))
-            topk_done.add(id(L))
+    if topk and _topk_batch_ok(topk):  # the plain layers in one call, the packed-wire layers in another
+        for packed in (False, True):
+            part = [e for e in topk if (e[0].compression_type == TOPK_PACKED_COMPRESSION_NAME) == packed]
+            if not part:
+                continue
+            y, plan = _decode_topk_batch(part, _gpu_for(out_dev), packed)
+            if out_dev.type == "cpu":
+                y = hostio.device_to_host(y, pool_memory=_HOST_POLICY)
+            for (L, *_), o, n in zip(part, plan.offsets, plan.sizes):
+                decoded[L.layer_name] = y[o:o + n].view(tuple(L.original_shape))
+                topk_done.add(id(L))
     out: Dict[str, torch.Tensor] = {}
     for layer in proto_layers:
         ct = layer.compression_type
-        if layer.layer_name in decoded and (ct in _QSGD_TYPES or (ct == TOPK_COMPRESSION_NAME and id(layer) in topk_done)):
+        if layer.layer_name in decoded and (ct in _QSGD_TYPES or (ct in _TOPK_TYPES and id(layer) in topk_done)):
             out[layer.layer_name] = decoded[layer.layer_name]
             continue
         base = None if base_updates is None else base_updates.get(layer.layer_name)
@@ -813,7 +937,10 @@ def decode_updates_into(proto_layers, targets: Dict[str, torch.Tensor]) -> None:
     groups, topk = _scan_layers(proto_layers)
     done = set()
     if topk and _topk_batch_ok(topk):
-        done = _overlay_topk_into(topk, targets)
+        for packed in (False, True):
+            part = [e for e in topk if (e[0].compression_type == TOPK_PACKED_COMPRESSION_NAME) == packed]
+            if part:
+                done |= _overlay_topk_into(part, targets, packed)
     for layers in groups.values():
         dev = _gpu_for(targets[layers[0].layer_name].device)
         y, plan = _decode_qsgd_batch(layers, dev)
@@ -828,13 +955,14 @@ def decode_updates_into(proto_layers, targets: Dict[str, torch.Tensor]) -> None:
         t.copy_(dec.to(t.dtype))
 
 
-def _overlay_topk_into(topk, targets) -> set:
+def _overlay_topk_into(topk, targets, packed: bool = False) -> set:
     """The Top-K part of decode_updates_into: the values set at their indices in each target
     (the reference's overlay on ``param.data``, global_grpc_client.py:98-111), in place.  Layers
     whose target is a contiguous fp32 GPU tensor of the layer's size are staged together (one
     chunked H2D), checked (one index check; an out-of-range index raises before any target is
     written) and scattered — as one launch when the targets are views of one arena, else one
-    launch per target.  Returns the ids of the layers handled; the caller decodes the rest."""
+    launch per target.  Returns the ids of the layers handled; the caller decodes the rest.
+    ``packed``: the layers are on the opt-in packed wire (their indices are unpacked as they are staged)."""
     first = targets[topk[0][0].layer_name]
     if not first.is_cuda:
         return set()
@@ -845,7 +973,8 @@ def _overlay_topk_into(topk, targets) -> set:
         return set()
     names = [L.layer_name for L, *_ in mine]
     plan = codec.Plan.get([_layer_numel(L) for L, *_ in mine], device=dev)
-    counts, values, indices = stage_topk([(v, i) for _L, v, i, _k in mine], dev, "topk_overlay")
+    counts, values, indices = stage_topk([(v, i) for _L, v, i, _k in mine], dev, "topk_overlay",
+                                         packed_plan=plan if packed else None)
     check_topk_indices(plan, counts, indices, names)
     dup = plan.topk_check_duplicates(counts, indices)
     flats = [targets[n].detach().reshape(-1) for n in names]
@@ -883,6 +1012,7 @@ __all__: List[str] = [
     "qsgd_layers_from_arena",
     "qsgd_packed_layer_from_payload",
     "topk_layer_from_bytes",
+    "topk_packed_layer_from_bytes",
     "topk_layer_from_payload",
     "wire_size",
 ]

@@ -7,7 +7,7 @@ from .core import (
     layerwise_decompress,
 )
 from .qsgd import QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGDQuantCompression
-from .topk import TOPK_COMPRESSION_NAME, TopKCompression
+from .topk import TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TopKCompression
 
 __all__ = [
     "Compression",
@@ -15,6 +15,7 @@ __all__ = [
     "ResidualUpdates",
     "TopKCompression",
     "TOPK_COMPRESSION_NAME",
+    "TOPK_PACKED_COMPRESSION_NAME",
     "QSGDQuantCompression",
     "QSGD_COMPRESSION_NAME",
     "QSGD_PACKED_COMPRESSION_NAME",

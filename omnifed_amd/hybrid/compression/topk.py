@@ -23,6 +23,9 @@ from ... import codec
 from .core import Compression, ResidualUpdates, compute_device, gather_arena, to_arena
 
 TOPK_COMPRESSION_NAME = "TopKCompression"
+# Opt-in wire (ours, not readable by the reference): the indices in max(1, bit_length(n - 1)) bits each
+# instead of int64; the values, the selection and its order are unchanged.
+TOPK_PACKED_COMPRESSION_NAME = "TopKBitPackedCompression"
 
 
 def topk_sparse(tensor: torch.Tensor, compress_ratio: float, tie_order: str = "torch"):
@@ -57,8 +60,10 @@ def topk_index_offset(K: int) -> int:
 class TopKCompression(Compression):
     """Top-k sparsification with error feedback (largest-magnitude elements)."""
 
-    def __init__(self, device="cpu", compress_ratio: float = 0.01, tie_order: str = "torch"):
+    def __init__(self, device="cpu", compress_ratio: float = 0.01, tie_order: str = "torch",
+                 packed_wire: bool = False):
         super().__init__()
+        self.packed_wire = bool(packed_wire)  # the wire layer sends TOPK_PACKED_COMPRESSION_NAME layers
         self.residual = ResidualUpdates()
         self.device = torch.device(device)
         self.compress_ratio = float(compress_ratio)

@@ -164,12 +164,14 @@ class DeviceAggregator:
         """Validate one update and stage its payloads in the device; the accumulator is not touched.
         Returns ``(q_args, t_args, adds)``: the QSGD arena ``(payload, width, level, norms, packed)`` or
         None, the Top-K selection ``(counts, values, indices)`` or None, and ``(name, tensor)`` dense terms.
+        An update's Top-K layers are all plain or all on the opt-in packed wire (``TopKBitPackedCompression``:
+        their indices are unpacked on the device as they are staged); mixed wires raise ValueError.
         ``packed``: the update's QSGD layers are ``QSGDBitPackedCompression`` ones, ``payload`` is the
         packed arena (``qsgd_pack``'s layout, tensor t at byte ``offsets[t] * b / 8``) and ``width`` the
         code's bits; an update's QSGD layers are all packed or all plain."""
         from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
                                                                   _validate_layer, check_topk_indices, stage_topk)
-        from .hybrid.compression import QSGD_PACKED_COMPRESSION_NAME
+        from .hybrid.compression import QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME
 
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
@@ -181,9 +183,9 @@ class DeviceAggregator:
             if got is not None:
                 topk_payload[L.layer_name] = got
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
-        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", "")
+        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", TOPK_PACKED_COMPRESSION_NAME, "")
         qsgd = [L for L in kept if L.compression_type in known[:2]]
-        topk = [L for L in kept if L.compression_type == "TopKCompression"]
+        topk = [L for L in kept if L.compression_type in known[2:4]]
         dense = [L for L in kept if L.compression_type == ""]
         if any(L.compression_type not in known for L in kept):
             bad = next(L for L in kept if L.compression_type not in known)
@@ -232,6 +234,15 @@ class DeviceAggregator:
         t_args = None
         # a Top-K layer with more values than its tensor's elements repeats indices: decoded alone
         # with numpy's last-wins rule (_decode_topk_layer), as decode_updates_dict does
+        topk_packed = bool(topk) and topk[0].compression_type == TOPK_PACKED_COMPRESSION_NAME
+        if any((L.compression_type == TOPK_PACKED_COMPRESSION_NAME) != topk_packed for L in topk):
+            raise ValueError("mixed Top-K wires (plain and bit-packed indices) within one update")
+        unpack_plan = self.plan if topk_packed else None  # stage_topk unpacks the indices on the device
+        if topk_packed:  # the index width is the tensor size's: the layer's shape must be the plan's
+            for L in topk:
+                n, m = self.plan.sizes[self.index[L.layer_name]], int(np.prod(tuple(L.original_shape)))
+                if m != n:
+                    raise ValueError(f"packed Top-K layer {L.layer_name!r}: shape of {m} elements, expected {n}")
         odd = [L for L in topk if topk_payload[L.layer_name][2] > self.plan.sizes[self.index[L.layer_name]]]
         odd_args = [(L.layer_name, _decode_topk_layer(L, device=self.device).reshape(-1)) for L in odd]
         topk = [L for L in topk if L not in odd]
@@ -241,7 +252,7 @@ class DeviceAggregator:
                 i = self.index[L.layer_name]
                 v, ix, k = topk_payload[L.layer_name]
                 pairs[i] = (v, ix)
-            counts, values, indices = stage_topk(pairs, self.device, "ps_topk")
+            counts, values, indices = stage_topk(pairs, self.device, "ps_topk", packed_plan=unpack_plan)
             check_topk_indices(self.plan, counts, indices, self.names)  # synchronises
             dup = self.plan.topk_check_duplicates(counts, indices).cpu()
             rep = [L for L in topk if dup[self.index[L.layer_name]]]
@@ -250,7 +261,7 @@ class DeviceAggregator:
                              for L in rep]
                 for L in rep:
                     pairs[self.index[L.layer_name]] = (b"", b"")
-                counts, values, indices = stage_topk(pairs, self.device, "ps_topk")
+                counts, values, indices = stage_topk(pairs, self.device, "ps_topk", packed_plan=unpack_plan)
                 check_topk_indices(self.plan, counts, indices, self.names)
             t_args = (counts, values, indices)
         dense_args = []

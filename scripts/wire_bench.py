@@ -13,7 +13,11 @@ apply_and_encode    : the PS's GetUpdatedModel: average + re-encode + LayerState
 host round trip     : host fp32 tensors in -> LayerStates -> host fp32 tensors out (the rate
                       including the H<->D copies, north_star)
 
-usage: python scripts/wire_bench.py [config] [out.json]
+The opt-in packed Top-K wire (TopKBitPackedCompression) has rows of its own, measured against the plain
+Top-K wire interleaved in this process (topk_packed_rows).
+
+usage: python scripts/wire_bench.py [config] [out.json] [topk_packed]
+       (a third argument "topk_packed": only the packed Top-K rows)
 """
 import json
 import sys
@@ -127,6 +131,46 @@ def leg(comp, tag):
     return r, layers
 
 
+def topk_packed_rows(rounds=5):
+    """The opt-in packed Top-K wire against the plain one, interleaved: per round one median of each of
+    encode_updates_dict and decode_updates_dict(device="cuda") on both wires, plain first then packed;
+    reported: the median, minimum and maximum over the rounds (the spread is this box's), the wire bytes and
+    the two index kernels alone (host-timed, launch included)."""
+    comps = {"plain": topk_comp(), "packed": topk_comp(packed_wire=True)}
+    lay = {k: encode_updates_dict(upd, c) for k, c in comps.items()}
+    rows = {k: {"encode_updates_dict_ms": [], "decode_updates_dict_gpu_ms": []} for k in comps}
+    for _ in range(rounds):
+        for k, c in comps.items():
+            rows[k]["encode_updates_dict_ms"].append(tm(lambda: encode_updates_dict(upd, c), reps=5, warm=2))
+        for k in comps:
+            rows[k]["decode_updates_dict_gpu_ms"].append(tm(lambda: decode_updates_dict(lay[k], device=dev), reps=5, warm=2))
+    out = {"rounds": rounds, "tie_order": TK_ORDER}
+    for k in comps:
+        out[k] = {m: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for m, v in rows[k].items()}
+        out[k]["values_bytes"] = sum(len(L.values_data) for L in lay[k])
+        out[k]["indices_bytes"] = sum(len(L.indices_data) for L in lay[k])
+        out[k]["wire_bytes"] = sum(L.ByteSize() for L in lay[k])
+    plan_p = codec.Plan.get([t.numel() for t in upd.values()], device=dev)
+    ks = plan_p.topk_ks(0.01)
+    idx = torch.cat([torch.randint(0, n, (k,), device=dev, generator=g) for n, k in zip(plan_p.sizes, ks)])
+    words = plan_p.topk_pack_indices(ks, idx)
+    back = torch.empty_like(idx)
+    out["device_pack_indices_ms"] = round(tm(lambda: plan_p.topk_pack_indices(ks, idx, packed_out=words), reps=10), 4)
+    out["device_unpack_indices_ms"] = round(tm(lambda: plan_p.topk_unpack_indices(ks, words, indices_out=back), reps=10), 4)
+    assert torch.equal(back, idx)
+    return out
+
+
+if len(sys.argv) > 3 and sys.argv[3] == "topk_packed":
+    progress("packed Top-K rows only")
+    res = {"config": cfg, "elements": N, "tensors": len(named), "copy_threads": hostio.workers(),
+           "topk_packed_wire": topk_packed_rows()}
+    print(json.dumps(res), flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    sys.exit(0)
+
 res = {"config": cfg, "elements": N, "tensors": len(named), "copy_threads": hostio.workers()}
 qcomp = build_global_compressor(enabled=True, scheme="qsgd", bit_width=4, device=dev)
 res["qsgd_s4"], layers = leg(qcomp, "qsgd")
@@ -229,6 +273,8 @@ pk = plan.qsgd_pack(qq, 8, 16)
 res["device_pack_ms"] = round(tm(lambda: plan.qsgd_pack(qq, 8, 16, packed_out=pk), reps=10), 4)
 res["device_decode_packed_ms"] = round(tm(lambda: plan.qsgd_decode_packed(pk, 16, nn, y_out=avg), reps=10), 4)
 res["device_decode_int8_ms"] = round(tm(lambda: plan.qsgd_decode(qq, 8, 16, nn, y_out=avg), reps=10), 4)
+progress("packed Top-K rows")
+res["topk_packed_wire"] = topk_packed_rows()
 line = json.dumps(res)
 print(line, flush=True)
 if out_path:
