@@ -64,7 +64,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 115
+#define OMF_ABI_VERSION 116
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -484,6 +484,47 @@ int omf_topk_pack_indices(omf_plan* plan, const int64_t* counts, const int64_t* 
                           void* stream);
 int omf_topk_unpack_indices(omf_plan* plan, const int64_t* counts, const uint32_t* packed, int64_t* indices,
                             void* stream);
+
+/*
+ * Opt-in quantised Top-K values ("TopKQuantPackedCompression"; ours: the reference sends every value as
+ * an fp32, global_grpc_compression.py:88-98, and cannot read this).  The k_t selected values of tensor t
+ * (fp32, the selection's order, packed per tensor at sum_{u<t} k_u as omf_topk_pack_indices' indices)
+ * become QSGD levels against the scale m_t = max |v|: q by omf_qsgd_encode's rule with the caller's norm
+ * m_t, L = 2^bit_width levels (bit_width = 1..8) and the Philox stream of (seed, offset) with "element"
+ * read as the position in tensor t's selection; code q + L in b = bit_width + 2 bits, LSB-first
+ * little-endian, value i at bits [i b, (i + 1) b) of the tensor's stream.  32 consecutive values of a
+ * tensor are b whole words; tensor t's stream starts at word b sum_{u<t} ceil(k_u / 32).  The receiver
+ * restores d = fl32(fl32(m_t q) / L), omf_qsgd_decode's rule.
+ *
+ * omf_topk_value_words (host only, counts a HOST array): the value arena's 32-bit words,
+ *   b sum_t ceil(k_t / 32), or -1 on bad counts, a bit_width outside 1..8 or a tensor of more than 2^32
+ *   elements.
+ * omf_topk_value_scales: scales[t] (float[nt], device) = max |v| over tensor t's values, exact and the
+ *   same for any launch shape (an unsigned maximum of the bits of |v| into words the call clears first:
+ *   a NaN among the values gives a NaN, an infinity an infinity); 0 for a tensor without a value.
+ * omf_topk_quantize_values: values, scales -> packed_values; the codes after a tensor's k_t-th value are
+ *   0 and every word of a quantised tensor is written.  With `residual` (the Top-K encoder's residual
+ *   arena, arena_end floats, which the encode left zero at the selected slots; or NULL) the quantisation
+ *   error fl32(v - d) is stored at residual[offsets[t] + index] for every value whose index is in
+ *   [0, n_t) (`indices` may be NULL without a residual).  Scale 0: every code is L, no draw is taken and
+ *   nothing is stored to the residual.  A scale that is NaN, infinite, negative or above FLT_MAX / L is
+ *   unusable: nothing is written for that tensor, neither codes nor residual (the sender keeps its fp32
+ *   values on the packed-index wire).
+ * omf_topk_dequantize_values: packed_values, scales -> the first k_t values of each tensor; the bits
+ *   past a tensor's k_t b are never used (a receiver's staging buffer is uninitialised there).  A tensor
+ *   whose scale is negative is skipped, its values left as they are: a message may mix quantised layers
+ *   and fp32-valued ones.
+ * The device calls are asynchronous on `stream`; sum k_t = 0 launches nothing (omf_topk_value_scales
+ * still clears the scales).  OMF_EINVAL: a NULL pointer, a buffer not 4-byte (indices: 8-byte) aligned,
+ * an output overlapping another buffer, bit_width outside 1..8, bad counts.
+ */
+int64_t omf_topk_value_words(omf_plan* plan, const int64_t* counts, int32_t bit_width);
+int omf_topk_value_scales(omf_plan* plan, const int64_t* counts, const float* values, float* scales, void* stream);
+int omf_topk_quantize_values(omf_plan* plan, const int64_t* counts, const float* values, const int64_t* indices,
+                             const float* scales, int32_t bit_width, uint64_t seed, uint64_t offset, float* residual,
+                             uint32_t* packed_values, void* stream);
+int omf_topk_dequantize_values(omf_plan* plan, const int64_t* counts, const uint32_t* packed_values,
+                               const float* scales, int32_t bit_width, float* values, void* stream);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,11 @@ SIGNATURES = {
     "omf_topk_packed_words": (_c_i64, [_c_p, ctypes.POINTER(_c_i64)]),
     "omf_topk_pack_indices": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
     "omf_topk_unpack_indices": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
+    "omf_topk_value_words": (_c_i64, [_c_p, ctypes.POINTER(_c_i64), _c_i32]),
+    "omf_topk_value_scales": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p]),
+    "omf_topk_quantize_values": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_p, _c_i32, _c_u64, _c_u64,
+                                                _c_p, _c_p, _c_p]),
+    "omf_topk_dequantize_values": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i64), _c_p, _c_p, _c_i32, _c_p, _c_p]),
 }
 
 _lock = threading.Lock()
@@ -100,7 +105,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 115 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 116 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

@@ -57,6 +57,23 @@ def topk_index_bits(numel: int) -> int:
     return max(1, (numel - 1).bit_length())
 
 
+def topk_value_bits(value_bits: int) -> int:
+    """Bits per code of the opt-in quantised Top-K value wire: ``value_bits`` + 2 = packed_bits(2^value_bits)
+    (levels q in [-L, L], L = 2^value_bits, sent as q + L); ``value_bits`` in 1..8."""
+    if isinstance(value_bits, bool) or int(value_bits) != value_bits or not 1 <= int(value_bits) <= 8:
+        raise ValueError(f"value_bits must be an integer in 1..8, not {value_bits!r}")
+    return int(value_bits) + 2
+
+
+FLT_MAX = 3.4028234663852886e38
+
+
+def topk_scale_usable(scale: float, value_bits: int) -> bool:
+    """The quantiser's rule for a tensor's scale m = max |v|: finite, and m · L does not overflow fp32
+    (m <= FLT_MAX / L, exact: L is a power of two).  The kernel and the sender decide alike."""
+    return 0.0 <= scale <= FLT_MAX / float(1 << int(value_bits))  # False for NaN
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -817,6 +834,96 @@ class Plan:
             check(lib().omf_topk_unpack_indices(self._h, arr, _ptr(packed), _ptr(indices_out), ctypes.c_void_p(st)),
                   "omf_topk_unpack_indices")
         return indices_out
+
+    # ------------------------------------------------------------ quantised Top-K values (opt-in)
+    def topk_value_layout(self, counts: Sequence[int], bit_width: int):
+        """``(b, vwoff, words)`` of the quantised value arena for the per-tensor ``counts``: every code in
+        ``b = bit_width + 2`` bits, tensor t's stream from 32-bit word ``vwoff[t]`` = b · Σ_{u<t} ceil(k_u / 32)
+        (a group of 32 values is b whole words), ``words`` in all (omf_topk_value_words)."""
+        b = topk_value_bits(bit_width)
+        key = tuple(int(c) for c in counts)
+        arr, _, _ = self._counts(key)
+        vwoff, cur = [], 0
+        for k in key:
+            vwoff.append(cur)
+            cur += -(-k // 32) * b
+        words = int(lib().omf_topk_value_words(self._h, arr, int(bit_width)))
+        if words != cur:
+            raise CodecError(f"omf_topk_value_words: {words} words, the layout rule gives {cur}")
+        return b, vwoff, words
+
+    def topk_value_words(self, counts: Sequence[int], bit_width: int) -> int:
+        return self.topk_value_layout(counts, bit_width)[2]
+
+    def topk_value_scales(self, counts: Sequence[int], values: torch.Tensor,
+                          scales_out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_topk_value_scales: ``scales[t]`` = max |v| over tensor t's ``counts[t]`` selected ``values``
+        (fp32, packed in plan order), exact; 0 for a tensor without a value, NaN / inf when the values
+        hold one.  Asynchronous."""
+        arr, ktot, _ = self._counts(counts)
+        dev = self.device
+        _need(values, "values", torch.float32, dev, ktot, 4)
+        if scales_out is None:
+            scales_out = torch.empty(self.nt, dtype=torch.float32, device=dev)
+        _need(scales_out, "scales_out", torch.float32, dev, self.nt, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_topk_value_scales(self._h, arr, _ptr(values), _ptr(scales_out), ctypes.c_void_p(st)),
+                  "omf_topk_value_scales")
+        return scales_out
+
+    def topk_quantize_values(self, counts: Sequence[int], values: torch.Tensor, indices: Optional[torch.Tensor],
+                             scales: torch.Tensor, bit_width: int, seed: int, offset: int,
+                             residual: Optional[torch.Tensor] = None, packed_out: Optional[torch.Tensor] = None,
+                             stream: Optional[int] = None) -> torch.Tensor:
+        """omf_topk_quantize_values: the selected ``values`` as QSGD levels against ``scales`` (2^bit_width
+        levels, the Philox stream of ``(seed, offset)`` over each tensor's selection), code q + L in
+        bit_width + 2 bits, into the value arena (an int32 tensor of ``topk_value_words`` words).  With
+        ``residual`` (the encoder's residual arena) the error fl32(v - d) is stored at each value's own slot.
+        A tensor whose scale is NaN, infinite or above FLT_MAX / L is left alone, codes and residual.
+        Asynchronous."""
+        arr, ktot, _ = self._counts(counts)
+        words = self.topk_value_words(counts, bit_width)
+        dev = self.device
+        _need(values, "values", torch.float32, dev, ktot, 4)
+        _need(scales, "scales", torch.float32, dev, self.nt, 4)
+        if indices is not None:
+            _need(indices, "indices", torch.int64, dev, ktot, 8)
+        if residual is not None:
+            if indices is None:
+                raise ValueError("a residual needs the indices")
+            _need(residual, "residual", torch.float32, dev, self.arena_end, 4)
+        if packed_out is None:
+            packed_out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+        _need(packed_out, "packed_out", torch.int32, dev, words, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_topk_quantize_values(self._h, arr, _ptr(values), _ptr(indices), _ptr(scales),
+                                                 int(bit_width), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                                                 _ptr(residual), _ptr(packed_out), ctypes.c_void_p(st)),
+                  "omf_topk_quantize_values")
+        return packed_out
+
+    def topk_dequantize_values(self, counts: Sequence[int], packed: torch.Tensor, scales: torch.Tensor,
+                               bit_width: int, values_out: Optional[torch.Tensor] = None,
+                               stream: Optional[int] = None) -> torch.Tensor:
+        """omf_topk_dequantize_values: the value arena back into fp32 values fl32(fl32(m_t q) / L)
+        (``counts[t]`` per tensor, packed in plan order); the bits past a tensor's last code are not used,
+        and a tensor with a negative scale keeps what ``values_out`` holds.  Asynchronous."""
+        arr, ktot, _ = self._counts(counts)
+        words = self.topk_value_words(counts, bit_width)
+        dev = self.device
+        _need(packed, "packed", torch.int32, dev, words, 4)
+        _need(scales, "scales", torch.float32, dev, self.nt, 4)
+        if values_out is None:
+            values_out = torch.empty(max(ktot, 1), dtype=torch.float32, device=dev)
+        _need(values_out, "values_out", torch.float32, dev, ktot, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_topk_dequantize_values(self._h, arr, _ptr(packed), _ptr(scales), int(bit_width),
+                                                   _ptr(values_out), ctypes.c_void_p(st)),
+                  "omf_topk_dequantize_values")
+        return values_out
 
 
 def div_(y: torch.Tensor, divisor: float, stream: Optional[int] = None) -> torch.Tensor:

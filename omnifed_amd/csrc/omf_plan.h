@@ -224,4 +224,13 @@ inline void* topk_table_counts(omf_plan* p, const int64_t* counts, size_t bytes,
 // 0 <= counts[t] <= sizes[t] for every tensor, *ktot their sum; else OMF_EINVAL (omf_topk_recv.hip).
 int topk_check_counts(const omf_plan* plan, const int64_t* counts, int64_t* ktot);
 
+// The plan's device tables of the packed wires for `counts` (koff, goff, the index wire's woff and bits;
+// uploaded on first use) and the host facts a call needs: the selection's values, its 32-value groups and
+// the index arena's words (omf_topk_pack.hip).  ktot = 0: no table, nothing to launch.
+struct PackArgs {
+  topk_layout::PackTable dev{};
+  int64_t ktot = 0, groups = 0, words = 0;
+};
+int topk_pack_args(omf_plan* plan, const int64_t* counts, PackArgs* out);
+
 }  // namespace omf

@@ -3,7 +3,7 @@
 // once for both, the encoder's constant tables and pipeline groups, the carve of the encode and
 // decode workspaces and of the plan-owned device tables, the decoder's tables, and the opt-in
 // bit-packed index wire (its width rule, the group pack / unpack the kernels and the host check share,
-// the packed arena's tables).
+// the packed arena's tables) with the quantised-value wire's layout rule beside it.
 //
 // Pure integer code: no HIP header, so tests/host/topk_layout_check.cpp runs it on a CPU under
 // sanitizers.  omf_topk.hip (the encoder) and omf_topk_recv.hip (decode and checks) upload what the
@@ -265,8 +265,10 @@ OMF_HD int32_t index_bits(int64_t n) {
   return b;
 }
 
-// One group: the low b bits of idx[0, nv) and code 0 for the rest of the 32, into the b words out[0, b).
-OMF_HD void pack_group(const int64_t* idx, int nv, int b, uint32_t* out) {
+// One group: the low b bits of idx[0, nv) and code 0 for the rest of the 32, into the b words out[0, b)
+// (T: the index wire's int64 indices, the value wire's 32-bit codes).
+template <class T>
+OMF_HD void pack_group(const T* idx, int nv, int b, uint32_t* out) {
   const uint64_t mask = (1ull << b) - 1ull;
   uint64_t acc = 0;
   int nb = 0, w = 0;
@@ -327,6 +329,19 @@ struct PackTable {
   int32_t* bits;
 };
 Carve<PackTable> pack_table_carve(int32_t nt);
+
+// ---------------------------------------------------------------- quantised values (opt-in wire)
+// "TopKQuantPackedCompression": the k selected values of a tensor as QSGD levels q in [-L, L], L = 2^s,
+// against the tensor's scale max |v|; code q + L in b = s + 2 bits, packed as the indices are: value i
+// at bits [i b, (i + 1) b) of the tensor's stream, a group of 32 consecutive values of one tensor in b
+// whole words.  b is the same for every tensor, so group g of the selection (g = goff[t] + j for tensor
+// t's j-th group: the index wire's goff) starts at word g b and the value arena holds goff[nt] b words.
+constexpr int kQvalMinBits = 1, kQvalMaxBits = 8;  // s
+
+// b = s + 2 = bit_length(2 L) (the packed QSGD wire's width for L levels); -1 outside s = 1..8.
+OMF_HD int32_t value_code_bits(int32_t s) { return s >= kQvalMinBits && s <= kQvalMaxBits ? s + 2 : -1; }
+OMF_HD int64_t value_group_word(int64_t g, int32_t b) { return g * (int64_t)b; }
+inline int64_t value_words(const PackTables& p, int32_t b) { return value_group_word(p.goff.back(), b); }
 
 }  // namespace topk_layout
 }  // namespace omf

@@ -22,18 +22,36 @@
 using namespace omf;
 using namespace omf::topk_layout;
 
-namespace {
+// The plan's device tables of the packed arena for `counts` (uploaded on first use; the last 8 count
+// vectors kept) and the host facts a call needs.  Shared with omf_topk_qval.hip (declared in omf_plan.h).
+int omf::topk_pack_args(omf_plan* plan, const int64_t* counts, PackArgs* out) {
+  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
+  if (int r = topk_check_counts(plan, counts, &out->ktot)) return r;
+  const PackTables h = pack_tables_host(plan->sizes, counts);
+  if (h.words < 0) return fail(OMF_EINVAL, "the packed Top-K wire takes tensors of at most 2^32 elements");
+  out->groups = h.goff.back();
+  out->words = h.words;
+  if (out->groups >= ((int64_t)1 << 32)) return fail(OMF_EINVAL, "the packed Top-K wire: too many indices");
+  if (out->ktot == 0) return OMF_OK;  // nothing to launch: no table either
+  DeviceGuard g(plan->device);
+  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
+  const Carve<PackTable> carve = pack_table_carve(plan->nt);
+  bool fresh = false;
+  uint64_t* host = nullptr;
+  void* d = topk_table_counts(plan, counts, carve.bytes(), &fresh, &host, kPackCountsKey);
+  if (!d) return fail(OMF_ENOMEM, "packed Top-K wire: table allocation failed");
+  out->dev = carve.bind(d);
+  if (fresh) {
+    const std::vector<uint32_t> goff32(h.goff.begin(), h.goff.end());
+    OMF_HIP(hipMemcpy(out->dev.koff, h.koff.data(), 8 * h.koff.size(), hipMemcpyHostToDevice));
+    OMF_HIP(hipMemcpy(out->dev.woff, h.woff.data(), 8 * h.woff.size(), hipMemcpyHostToDevice));
+    OMF_HIP(hipMemcpy(out->dev.goff, goff32.data(), 4 * goff32.size(), hipMemcpyHostToDevice));
+    OMF_HIP(hipMemcpy(out->dev.bits, h.bits.data(), 4 * h.bits.size(), hipMemcpyHostToDevice));
+  }
+  return OMF_OK;
+}
 
-// A group's tensor: the largest t with goff[t] <= g (a tensor without groups shares its goff with the
-// next one, the larger t), goff staged in LDS when it fits, as topk_dec_place stages its koff window.
-__device__ __forceinline__ int group_tensor(const uint32_t* __restrict__ goff_g, uint32_t* s_goff, int nt, int64_t g) {
-  return nt <= kArenaMaxTensors ? koff_tensor(s_goff, 0, nt - 1, g) : koff_tensor(goff_g, 0, nt - 1, g);
-}
-__device__ __forceinline__ void stage_goff(const uint32_t* __restrict__ goff_g, uint32_t* s_goff, int nt) {
-  if (nt > kArenaMaxTensors) return;  // uniform
-  for (int t = threadIdx.x; t <= nt; t += kThreads) s_goff[t] = goff_g[t];
-  __syncthreads();
-}
+namespace {
 
 // One thread per group: its (at most 32) int64 indices read directly, as qsgd_pack reads its levels, and
 // packed into b whole words — the code of an index is its low b bits, the codes after the tensor's k_t-th
@@ -113,40 +131,6 @@ __global__ __launch_bounds__(kThreads) void topk_unpack_idx(const uint32_t* __re
   }
 }
 
-// The plan's device tables of the packed arena for `counts` (uploaded on first use; the last 8 count
-// vectors kept) and the host facts a call needs.
-struct PackArgs {
-  PackTable dev{};
-  int64_t ktot = 0, groups = 0, words = 0;
-};
-
-int pack_args(omf_plan* plan, const int64_t* counts, PackArgs* out) {
-  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
-  if (int r = topk_check_counts(plan, counts, &out->ktot)) return r;
-  const PackTables h = pack_tables_host(plan->sizes, counts);
-  if (h.words < 0) return fail(OMF_EINVAL, "the packed Top-K wire takes tensors of at most 2^32 elements");
-  out->groups = h.goff.back();
-  out->words = h.words;
-  if (out->groups >= ((int64_t)1 << 32)) return fail(OMF_EINVAL, "the packed Top-K wire: too many indices");
-  if (out->ktot == 0) return OMF_OK;  // nothing to launch: no table either
-  DeviceGuard g(plan->device);
-  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
-  const Carve<PackTable> carve = pack_table_carve(plan->nt);
-  bool fresh = false;
-  uint64_t* host = nullptr;
-  void* d = topk_table_counts(plan, counts, carve.bytes(), &fresh, &host, kPackCountsKey);
-  if (!d) return fail(OMF_ENOMEM, "packed Top-K wire: table allocation failed");
-  out->dev = carve.bind(d);
-  if (fresh) {
-    const std::vector<uint32_t> goff32(h.goff.begin(), h.goff.end());
-    OMF_HIP(hipMemcpy(out->dev.koff, h.koff.data(), 8 * h.koff.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->dev.woff, h.woff.data(), 8 * h.woff.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->dev.goff, goff32.data(), 4 * goff32.size(), hipMemcpyHostToDevice));
-    OMF_HIP(hipMemcpy(out->dev.bits, h.bits.data(), 4 * h.bits.size(), hipMemcpyHostToDevice));
-  }
-  return OMF_OK;
-}
-
 // The pointer rules of both calls: non-NULL, packed 4-byte and indices 8-byte aligned, disjoint.
 int check_buffers(const PackArgs& a, const void* indices, const void* packed) {
   if (!indices || !packed) return fail(OMF_EINVAL, "indices and packed must be non-NULL");
@@ -172,7 +156,7 @@ int64_t omf_topk_packed_words(omf_plan* plan, const int64_t* counts) {
 int omf_topk_pack_indices(omf_plan* plan, const int64_t* counts, const int64_t* indices, uint32_t* packed,
                           void* stream) {
   PackArgs a;
-  if (int r = pack_args(plan, counts, &a)) return r;
+  if (int r = topk_pack_args(plan, counts, &a)) return r;
   if (a.ktot == 0) return OMF_OK;
   if (int r = check_buffers(a, indices, packed)) return r;
   DeviceGuard g(plan->device);
@@ -188,7 +172,7 @@ int omf_topk_pack_indices(omf_plan* plan, const int64_t* counts, const int64_t* 
 int omf_topk_unpack_indices(omf_plan* plan, const int64_t* counts, const uint32_t* packed, int64_t* indices,
                             void* stream) {
   PackArgs a;
-  if (int r = pack_args(plan, counts, &a)) return r;
+  if (int r = topk_pack_args(plan, counts, &a)) return r;
   if (a.ktot == 0) return OMF_OK;
   if (int r = check_buffers(a, indices, packed)) return r;
   DeviceGuard g(plan->device);

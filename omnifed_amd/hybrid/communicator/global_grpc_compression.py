@@ -41,8 +41,8 @@ from ..compression.qsgd import (
     choose_qsgd_storage_width,
     should_compress_tensor,
 )
-from ..compression.topk import (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TopKCompression,
-                                topk_index_offset)
+from ..compression.topk import (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME,
+                                TopKCompression, topk_index_offset)
 from ..compression.core import compute_device
 from ... import codec, hostio
 
@@ -51,7 +51,9 @@ GlobalHybridCompressor = Union[TopKCompression, QSGDQuantCompression]
 _QSGD_NUMPY_DTYPES = {8: np.int8, 32: np.int32}
 _QSGD_TORCH_DTYPES = {8: torch.int8, 32: torch.int32}
 _QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME)
-_TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME)
+_TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
+# the two types that share the packed index wire: a message or an update may mix them
+_TOPK_PACKED_TYPES = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
 
 
 _STAGING = hostio.STAGING
@@ -88,16 +90,22 @@ def compression_mode_name(compressor: Optional[GlobalHybridCompressor]) -> str:
 
 
 def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_ratio: float = 0.01,
-                            bit_width: int = 8, device="cpu", packed_wire: bool = False) -> Optional[GlobalHybridCompressor]:
+                            bit_width: int = 8, device="cpu", packed_wire: bool = False,
+                            value_bits=None) -> Optional[GlobalHybridCompressor]:
     """global_grpc_compression.py:35-52.  ``packed_wire`` (default off): the scheme's opt-in bit-packed
     wire — ``QSGDBitPackedCompression`` (the levels in ceil(log2(2L + 1)) bits) or
     ``TopKBitPackedCompression`` (the indices in max(1, bit_length(n - 1)) bits); neither is readable
-    by the reference."""
+    by the reference.  ``value_bits`` (default None; needs ``scheme="topk"`` and ``packed_wire=True``):
+    ``TopKQuantPackedCompression`` layers, the selected values as QSGD levels of 2^value_bits against
+    max |v| in value_bits + 2 bits each, the quantisation error fed back through the residual."""
     if not enabled:
         return None
     scheme_norm = str(scheme).lower()
+    if value_bits is not None and scheme_norm != "topk":
+        raise ValueError(f"value_bits requires scheme='topk' (got scheme={scheme!r})")
     if scheme_norm == "topk":
-        return TopKCompression(device=device, compress_ratio=float(compress_ratio), packed_wire=bool(packed_wire))
+        return TopKCompression(device=device, compress_ratio=float(compress_ratio), packed_wire=bool(packed_wire),
+                               value_bits=value_bits)
     if scheme_norm == "qsgd":
         return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire))
     raise ValueError(f"Unsupported global_compression.scheme={scheme!r}; expected 'topk' or 'qsgd'")
@@ -134,8 +142,9 @@ def hybrid_global_compressor_from_cfg(cfg, device="cpu") -> Optional[GlobalHybri
     ratio = float(_select(cfg, "engine.hybrid.global_compression.compress_ratio", 0.01))
     bit_width = int(_select(cfg, "engine.hybrid.global_compression.bit_width", 8))
     packed = bool(_select(cfg, "engine.hybrid.global_compression.packed_wire", False))  # opt-in, ours
+    value_bits = _select(cfg, "engine.hybrid.global_compression.value_bits", None)  # opt-in, ours
     return build_global_compressor(enabled=enabled, scheme=scheme, compress_ratio=ratio, bit_width=bit_width,
-                                   device=device, packed_wire=packed)
+                                   device=device, packed_wire=packed, value_bits=value_bits)
 
 
 # ---------------------------------------------------------------- layer builders (host)
@@ -219,6 +228,29 @@ def topk_packed_layer_from_bytes(name: str, shape, values: bytes, packed: bytes)
     return layer
 
 
+def topk_quant_layer_from_bytes(name: str, shape, k: int, codes: bytes, packed: bytes, scale: float, value_bits: int):
+    """The opt-in quantised Top-K ``LayerState``: the packed Top-K layer's indices, and ``values_data`` = the k
+    codes q + L (L = 2^value_bits) in value_bits + 2 bits each, LSB first, the first ceil(k b / 8) bytes of the
+    stream; the scale max |v| in ``meta_tensor``, L in ``level``, and k in ``param_shape`` (both payloads are bit
+    streams: no byte length gives it)."""
+    layer = topk_packed_layer_from_bytes(name, shape, codes, packed)
+    layer.compression_type = TOPK_QUANT_COMPRESSION_NAME
+    layer.values_dtype = f"packed.q{codec.topk_value_bits(value_bits)}"
+    layer.meta_tensor = np.array([float(scale)], dtype=np.float32).tobytes()
+    layer.meta_tensor_dtype = "torch.float32"
+    layer.level = 1 << int(value_bits)
+    layer.param_shape.append(int(k))
+    return layer
+
+
+def _refuse_half_values(tensors, compressor) -> None:
+    """The value quantiser serves the fp32 arena path (fp32 and integer tensors)."""
+    if compressor.value_bits is not None:
+        for t in tensors:
+            if isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16):
+                raise ValueError(f"value_bits quantises fp32 (or integer) tensors, not {t.dtype}")
+
+
 def _weighted(tensor: torch.Tensor, weight) -> torch.Tensor:
     """``torch.mul(tensor, batch_samples)`` of GrpcCommunicator.aggregate (global_grpc.py:104, 121)."""
     return tensor if weight is None else torch.mul(tensor.detach(), weight)
@@ -229,9 +261,17 @@ def _alpha(weight) -> float:
 
 
 def _encode_topk_layer(name: str, tensor: torch.Tensor, compressor: TopKCompression, weight=None):
+    _refuse_half_values([tensor], compressor)
     if compressor.packed_wire and _topk_batchable([tensor]):
         return _encode_topk_updates({name: tensor}, compressor, weight)[0]  # a one-tensor plan, packed on the device
     (values, indices), _ctx = compressor.compress_weighted(tensor.detach(), name, _alpha(weight))
+    if compressor.value_bits is not None:  # an integer tensor: its fp32 selection through a one-tensor plan
+        dev = compute_device(tensor, compressor.device)
+        plan = codec.Plan.get([tensor.numel()], device=dev)
+        k = indices.numel()
+        return _quant_topk_layers(plan, values.detach().to(dev, torch.float32).contiguous(),
+                                  indices.detach().to(dev, torch.int64).contiguous(), [k], [0, k], [name],
+                                  {name: tensor}, compressor, compressor.residual.residuals[name])[0]
     if compressor.packed_wire:  # (a bf16 tensor fails in .numpy() as on the plain wire)
         vals = np.ascontiguousarray(values.detach().cpu().numpy(), dtype=np.float32).tobytes()
         n, k = tensor.numel(), indices.numel()
@@ -314,6 +354,19 @@ def _unpack_topk_indices(packed: bytes, k: int, numel: int, dev: torch.device) -
     return plan.topk_unpack_indices([k], torch.from_numpy(raw.view(np.int32)).to(dev))[:k].cpu().numpy()
 
 
+def _dequantize_topk_values(qv: "QuantValues", numel: int, dev: torch.device) -> np.ndarray:
+    """The k fp32 values of a quantised layer (checked by read_topk_layer): a one-tensor dequantise on the GPU."""
+    if qv.k == 0:
+        return np.zeros(0, dtype=np.float32)
+    plan = codec.Plan.get([numel], device=dev)
+    words = plan.topk_value_words([qv.k], qv.bits)
+    raw = np.zeros(4 * words, dtype=np.uint8)
+    raw[:len(qv.codes)] = np.frombuffer(qv.codes, dtype=np.uint8)
+    scale = torch.tensor([qv.scale], dtype=torch.float32, device=dev)
+    out = plan.topk_dequantize_values([qv.k], torch.from_numpy(raw.view(np.int32)).to(dev), scale, qv.bits)
+    return out[:qv.k].cpu().numpy()
+
+
 def _decode_topk_layer(layer, *, base_tensor: Optional[torch.Tensor] = None, device=None,
                        last_wins: bool = False) -> torch.Tensor:
     """global_grpc_compression.py:140-160: overlay on ``base_tensor`` or zero-filled dense.
@@ -321,11 +374,16 @@ def _decode_topk_layer(layer, *, base_tensor: Optional[torch.Tensor] = None, dev
     value per index (always applied when there are more values than elements)."""
     original_shape = tuple(layer.original_shape)
     numel = int(np.prod(original_shape))
-    if layer.compression_type == TOPK_PACKED_COMPRESSION_NAME:
-        # the packed wire: back to the int64 indices the plain wire carries, then the plain layer's code
+    if layer.compression_type in _TOPK_PACKED_TYPES:
+        # the packed wires: back to the fp32 values and int64 indices the plain wire carries, then the plain
+        # layer's code
         vbytes, packed, k = read_topk_layer(layer)
-        values = np.frombuffer(vbytes, dtype=np.float32)
-        indices = _unpack_topk_indices(packed, k, numel, _gpu_for(_out_device(base_tensor, device)))
+        gpu = _gpu_for(_out_device(base_tensor, device))
+        if isinstance(vbytes, QuantValues):  # (k <= n: read_topk_layer)
+            values = _dequantize_topk_values(vbytes, numel, gpu)
+        else:
+            values = np.frombuffer(vbytes, dtype=np.float32)
+        indices = _unpack_topk_indices(packed, k, numel, gpu)
     else:
         if not layer.values_data or not layer.indices_data:
             raise ValueError(f"Compressed layer {layer.layer_name!r} missing values/indices")
@@ -483,6 +541,8 @@ def wire_size(layers) -> Dict[str, int]:
             payload += _payload_nbytes(L)
         else:
             payload += len(L.values_data) + len(L.indices_data) + 4 * len(L.param_update)
+            if L.compression_type == TOPK_QUANT_COMPRESSION_NAME:
+                payload += len(L.meta_tensor)  # the scale
         shape = tuple(L.original_shape) or tuple(L.param_shape)
         dense += 4 * int(np.prod(shape)) if shape else 0
     return {"wire_bytes": wire, "payload_bytes": payload, "dense_fp32_bytes": dense, "layers": len(layers)}
@@ -518,11 +578,15 @@ def _encode_topk_updates(updates, compressor: TopKCompression, weight) -> list:
     global_grpc_compression.py:84-98 / 207-211 (the selection does not depend on the batching)."""
     names = list(updates.keys())
     flats = [updates[n].detach().reshape(-1) for n in names]
+    _refuse_half_values(flats, compressor)
     plan, values, indices, ks = compressor.encode_arena(names, flats, _alpha(weight))
     nt = len(names)
     koff = [0]
     for k in ks:
         koff.append(koff[-1] + k)
+    if compressor.value_bits is not None:
+        return _quant_topk_layers(plan, values, indices, ks, koff, names, updates, compressor,
+                                  compressor.residual_arena(names, plan))
     if compressor.packed_wire:
         return _packed_topk_layers(plan, values, indices, ks, koff, names, updates, compressor)
     io = topk_index_offset(koff[-1])
@@ -558,6 +622,45 @@ def _packed_topk_layers(plan, values, indices, ks, koff, names, updates, compres
     spans = [(4 * woff[t], (ks[t] * bits[t] + 7) // 8) for t in range(nt)]
     for t, payload in hostio.device_to_bytes(words, spans, key="topk_encode_idx"):
         layers[t] = topk_packed_layer_from_bytes(names[t], tuple(updates[names[t]].shape), vals[t], payload)
+        vals[t] = None
+    if compressor.tie_order != "torch":
+        plan.check()
+    return layers
+
+
+def _quant_topk_layers(plan, values, indices, ks, koff, names, updates, compressor, residual) -> list:
+    """The opt-in quantised wire of an encoded arena (``value_bits``): the scales max |v| (one launch, one small
+    device-to-host copy: they go on the wire and decide the fallback), then ONE ``topk_quantize_values`` — the
+    codes, and the quantisation error into ``residual`` at the selected slots, which the encode left zero — and
+    the index pack; codes and index words device to host.  The fp32 values stay on the device, except those of
+    a tensor whose scale is unusable (NaN, infinite, or its product with L overflows): that layer goes out as a
+    ``TopKBitPackedCompression`` one, its residual untouched by the quantiser."""
+    s = compressor.value_bits
+    nt = len(names)
+    bits, woff, _ = plan.topk_packed_layout(ks)  # ValueError for a tensor above 2^32 elements
+    b, vwoff, _ = plan.topk_value_layout(ks, s)
+    scales = plan.topk_value_scales(ks, values)
+    sh = scales.cpu().numpy()  # synchronises
+    codes = plan.topk_quantize_values(ks, values, indices, scales, s, compressor.philox_key(), compressor._next_call(),
+                                      residual=residual)
+    words = plan.topk_pack_indices(ks, indices)
+    ok = [codec.topk_scale_usable(float(sh[t]), s) for t in range(nt)]
+    vals: List[Optional[bytes]] = [None] * nt
+    if not all(ok):  # the fallback layers' fp32 values
+        spans = [(4 * koff[t], 0 if ok[t] else 4 * ks[t]) for t in range(nt)]
+        for t, payload in hostio.device_to_bytes(values, spans, key="topk_encode"):
+            vals[t] = payload
+    spans = [(4 * vwoff[t], (ks[t] * b + 7) // 8 if ok[t] else 0) for t in range(nt)]
+    for t, payload in hostio.device_to_bytes(codes, spans, key="topk_encode_val"):
+        vals[t] = payload
+    layers: List = [None] * nt
+    spans = [(4 * woff[t], (ks[t] * bits[t] + 7) // 8) for t in range(nt)]
+    for t, payload in hostio.device_to_bytes(words, spans, key="topk_encode_idx"):
+        shape = tuple(updates[names[t]].shape)
+        if ok[t]:
+            layers[t] = topk_quant_layer_from_bytes(names[t], shape, ks[t], vals[t], payload, float(sh[t]), s)
+        else:
+            layers[t] = topk_packed_layer_from_bytes(names[t], shape, vals[t], payload)
         vals[t] = None
     if compressor.tie_order != "torch":
         plan.check()
@@ -722,6 +825,53 @@ def _decode_qsgd_to_host(layers, dev: torch.device):
     return out, plan
 
 
+class QuantValues:
+    """The values of a ``TopKQuantPackedCompression`` layer as read_topk_layer returns them, in the place of the
+    fp32 value bytes: the code bytes, the count k (the layer's ``param_shape[0]``), the scale and value_bits."""
+
+    __slots__ = ("codes", "k", "scale", "bits")
+
+    def __init__(self, codes: bytes, k: int, scale: float, bits: int):
+        self.codes, self.k, self.scale, self.bits = codes, int(k), float(scale), int(bits)
+
+
+def _nvalues(v) -> int:
+    return v.k if isinstance(v, QuantValues) else len(v) // 4
+
+
+def _read_quant_topk(layer, v: bytes, i: bytes):
+    """read_topk_layer for the opt-in quantised wire: ``(QuantValues, packed index bytes, k)`` once the fields
+    agree: ``level`` a power of two L in 2..256, ``values_dtype`` "packed.q{b}" with b = log2 L + 2, k =
+    ``param_shape[0]`` at most the layer's elements, ``values_data`` exactly ceil(k b / 8) bytes, the indices
+    as on the packed wire for that k, and ``meta_tensor`` one finite fp32 scale that is not negative."""
+    name = layer.layer_name
+    L = int(layer.level)
+    if not (2 <= L <= 256 and L & (L - 1) == 0):
+        raise ValueError(f"Compressed layer {name!r} has invalid level={L} (a power of two in 2..256)")
+    s = L.bit_length() - 1
+    b = s + 2
+    if layer.values_dtype != f"packed.q{b}":
+        raise ValueError(f"Compressed layer {name!r} has unsupported values_dtype={layer.values_dtype!r} "
+                         f"(expected 'packed.q{b}')")
+    if len(layer.param_shape) != 1 or layer.param_shape[0] < 0:
+        raise ValueError(f"Compressed layer {name!r}: param_shape must hold the value count, not "
+                         f"{list(layer.param_shape)}")
+    k, n = int(layer.param_shape[0]), _layer_numel(layer)
+    if k > n:
+        raise ValueError(f"Compressed layer {name!r}: {k} values for {n} elements")
+    if len(v) != (k * b + 7) // 8:
+        raise ValueError(f"Compressed layer {name!r}: {len(v)} value bytes, expected {(k * b + 7) // 8} "
+                         f"for {k} values of {b} bits")
+    _check_packed_indices(layer, i, k, n)
+    if len(layer.meta_tensor) != 4:
+        raise ValueError(f"Compressed layer {name!r}: meta_tensor (the scale) must be one float32, not "
+                         f"{len(layer.meta_tensor)} bytes")
+    m = np.frombuffer(layer.meta_tensor, dtype=np.float32)[0]
+    if not np.isfinite(m) or np.signbit(m):
+        raise ValueError(f"Compressed layer {name!r} has invalid scale={float(m)!r} (finite and not negative)")
+    return QuantValues(v, k, float(m), s), i, k
+
+
 def _read_packed_topk(layer, v: bytes, i: bytes):
     """read_topk_layer for the opt-in packed wire: ``(values bytes, packed index bytes, k)`` once the
     fields agree with the layer's own shape — width and indices_dtype are max(1, bit_length(n - 1)) and
@@ -730,6 +880,13 @@ def _read_packed_topk(layer, v: bytes, i: bytes):
     if len(v) % 4:
         raise ValueError(f"Compressed layer {name!r}: buffer size must be a multiple of element size")
     k, n = len(v) // 4, _layer_numel(layer)
+    _check_packed_indices(layer, i, k, n)
+    return v, i, k
+
+
+def _check_packed_indices(layer, i: bytes, k: int, n: int) -> None:
+    """The packed index fields of a layer of n elements carrying k values."""
+    name = layer.layer_name
     try:
         b = codec.topk_index_bits(n)
     except ValueError:
@@ -742,7 +899,6 @@ def _read_packed_topk(layer, v: bytes, i: bytes):
     if len(i) != (k * b + 7) // 8:
         raise ValueError(f"Compressed layer {name!r}: {len(i)} index bytes, expected {(k * b + 7) // 8} "
                          f"for {k} values of {b} bits")
-    return v, i, k
 
 
 def read_topk_layer(layer):
@@ -756,6 +912,8 @@ def read_topk_layer(layer):
         raise ValueError(f"Compressed layer {layer.layer_name!r} missing values/indices")
     if layer.compression_type == TOPK_PACKED_COMPRESSION_NAME:
         return _read_packed_topk(layer, v, i)
+    if layer.compression_type == TOPK_QUANT_COMPRESSION_NAME:
+        return _read_quant_topk(layer, v, i)
     if len(v) % 4 or len(i) % 8:
         raise ValueError(f"Compressed layer {layer.layer_name!r}: buffer size must be a multiple of element size")
     if len(v) // 4 != len(i) // 8:
@@ -809,7 +967,8 @@ def _topk_batch_ok(topk) -> bool:
         if n < 1 or k > n or L.layer_name in names:
             return False
         names.add(L.layer_name)
-    return True
+    # the quantised layers of one staging share a code width (a message of several levels: layer by layer)
+    return len({v.bits for _L, v, _i, _k in topk if isinstance(v, QuantValues)}) <= 1
 
 
 def stage_topk(pairs, dev: torch.device, key: str, packed_plan=None):
@@ -823,8 +982,12 @@ def stage_topk(pairs, dev: torch.device, key: str, packed_plan=None):
     its tensor's size).  The index bytes are then each layer's packed ``indices_data``, staged into a packed
     region behind the int64 region — tensor t's at byte 4 * woff[t]; what follows its bytes in its last
     group stays uninitialised — and ``topk_unpack_indices`` fills the int64 region on the device: 4 k + about
-    3 k bytes cross PCIe instead of 12 k.  From there on the message is a plain one."""
-    counts = [len(v) // 4 for v, _ in pairs]
+    3 k bytes cross PCIe instead of 12 k.  From there on the message is a plain one.  A pair whose values are a
+    ``QuantValues`` (a ``TopKQuantPackedCompression`` layer; all of one value_bits) has its codes staged into a
+    third region, tensor t's at the byte 4 * vwoff[t] of the value arena, and ONE ``topk_dequantize_values``
+    writes their fp32 values into the values region; the tensors that sent fp32 values carry the scale -1,
+    which the kernel skips."""
+    counts = [_nvalues(v) for v, _ in pairs]
     koff = [0]
     for k in counts:
         koff.append(koff[-1] + k)
@@ -833,9 +996,25 @@ def stage_topk(pairs, dev: torch.device, key: str, packed_plan=None):
     if packed_plan is not None:
         _, woff, words = packed_plan.topk_packed_layout(counts)
         po = (io + 8 * K + 255) // 256 * 256  # the packed region: past the int64 one
-        buf = torch.empty(max(po + 4 * words, 256), dtype=torch.uint8, device=dev)
-        items = [(4 * koff[t], (lambda v=v: v)) for t, (v, _) in enumerate(pairs)]
+        quant = [t for t, (v, _) in enumerate(pairs) if isinstance(v, QuantValues)]
+        vo, vwords, s = (po + 4 * words + 255) // 256 * 256, 0, 0  # the code region: past the packed one
+        if quant:
+            s = pairs[quant[0]][0].bits
+            if any(pairs[t][0].bits != s for t in quant):
+                raise ValueError("quantised Top-K layers of different levels in one staging")
+            _, vwoff, vwords = packed_plan.topk_value_layout(counts, s)
+        buf = torch.empty(max(vo + 4 * vwords, 256), dtype=torch.uint8, device=dev)
+        items = [(4 * koff[t], (lambda v=v: b"" if isinstance(v, QuantValues) else v)) for t, (v, _) in enumerate(pairs)]
         hostio.bytes_to_device(items, buf, 4 * K, key=key)
+        if quant and K:
+            vregion = buf[vo:vo + 4 * vwords]
+            hostio.bytes_to_device([(4 * vwoff[t], (lambda t=t: pairs[t][0].codes)) for t in quant], vregion, 4 * vwords,
+                                   key=key + "_val")
+            scales = np.full(len(pairs), -1.0, dtype=np.float32)
+            for t in quant:
+                scales[t] = pairs[t][0].scale
+            packed_plan.topk_dequantize_values(counts, vregion.view(torch.int32), torch.from_numpy(scales).to(dev), s,
+                                               values_out=buf[:4 * K].view(torch.float32))
         region = buf[po:po + 4 * words]
         items = [(4 * woff[t], (lambda i=i: i)) for t, (_, i) in enumerate(pairs)]
         hostio.bytes_to_device(items, region, 4 * words, key=key + "_idx")
@@ -905,7 +1084,7 @@ def decode_updates_dict(proto_layers, *, base_updates: Optional[Dict[str, torch.
         topk = [e for e in topk if e[0].layer_name not in base_updates]
     if topk and _topk_batch_ok(topk):  # the plain layers in one call, the packed-wire layers in another
         for packed in (False, True):
-            part = [e for e in topk if (e[0].compression_type == TOPK_PACKED_COMPRESSION_NAME) == packed]
+            part = [e for e in topk if (e[0].compression_type in _TOPK_PACKED_TYPES) == packed]
             if not part:
                 continue
             y, plan = _decode_topk_batch(part, _gpu_for(out_dev), packed)
@@ -938,7 +1117,7 @@ def decode_updates_into(proto_layers, targets: Dict[str, torch.Tensor]) -> None:
     done = set()
     if topk and _topk_batch_ok(topk):
         for packed in (False, True):
-            part = [e for e in topk if (e[0].compression_type == TOPK_PACKED_COMPRESSION_NAME) == packed]
+            part = [e for e in topk if (e[0].compression_type in _TOPK_PACKED_TYPES) == packed]
             if part:
                 done |= _overlay_topk_into(part, targets, packed)
     for layers in groups.values():
@@ -1013,6 +1192,7 @@ __all__: List[str] = [
     "qsgd_packed_layer_from_payload",
     "topk_layer_from_bytes",
     "topk_packed_layer_from_bytes",
+    "topk_quant_layer_from_bytes",
     "topk_layer_from_payload",
     "wire_size",
 ]

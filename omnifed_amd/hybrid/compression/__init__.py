@@ -7,7 +7,8 @@ from .core import (
     layerwise_decompress,
 )
 from .qsgd import QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGDQuantCompression
-from .topk import TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TopKCompression
+from .topk import (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME,
+                   TopKCompression)
 
 __all__ = [
     "Compression",
@@ -16,6 +17,7 @@ __all__ = [
     "TopKCompression",
     "TOPK_COMPRESSION_NAME",
     "TOPK_PACKED_COMPRESSION_NAME",
+    "TOPK_QUANT_COMPRESSION_NAME",
     "QSGDQuantCompression",
     "QSGD_COMPRESSION_NAME",
     "QSGD_PACKED_COMPRESSION_NAME",

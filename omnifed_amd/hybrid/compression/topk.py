@@ -17,15 +17,24 @@ agree when ties stay inside the selection, and in the nth_element regime k*64 > 
 
 from __future__ import annotations
 
+import itertools
+
 import torch
 
 from ... import codec
 from .core import Compression, ResidualUpdates, compute_device, gather_arena, to_arena
+from .qsgd import client_identity, philox_key
 
 TOPK_COMPRESSION_NAME = "TopKCompression"
 # Opt-in wire (ours, not readable by the reference): the indices in max(1, bit_length(n - 1)) bits each
 # instead of int64; the values, the selection and its order are unchanged.
 TOPK_PACKED_COMPRESSION_NAME = "TopKBitPackedCompression"
+# Opt-in wire on top of the packed one (ours): the selected values as QSGD levels against max |v|, code
+# q + L in value_bits + 2 bits; the quantisation error goes to the residual.
+TOPK_QUANT_COMPRESSION_NAME = "TopKQuantPackedCompression"
+
+
+_INSTANCES = itertools.count()  # creation index of a compressor: part of its Philox key (value_bits)
 
 
 def topk_sparse(tensor: torch.Tensor, compress_ratio: float, tie_order: str = "torch"):
@@ -61,9 +70,23 @@ class TopKCompression(Compression):
     """Top-k sparsification with error feedback (largest-magnitude elements)."""
 
     def __init__(self, device="cpu", compress_ratio: float = 0.01, tie_order: str = "torch",
-                 packed_wire: bool = False):
+                 packed_wire: bool = False, value_bits=None):
         super().__init__()
         self.packed_wire = bool(packed_wire)  # the wire layer sends TOPK_PACKED_COMPRESSION_NAME layers
+        # value_bits = s (1..8): the wire layer sends TOPK_QUANT_COMPRESSION_NAME layers, the values as QSGD
+        # levels of L = 2^s against max |v|.  The draws are the Philox stream of (philox_key(), a call counter):
+        # the batched path advances the counter once per encode_updates_dict and draws tensor t's from stream
+        # t (its plan index); the per-layer path advances it once per layer and draws from stream 0 — so the
+        # two paths give different, equally valid codes.
+        if value_bits is not None:
+            codec.topk_value_bits(value_bits)  # ValueError outside 1..8
+            if not self.packed_wire:
+                raise ValueError("value_bits requires packed_wire=True (the quantised values ride the packed Top-K wire)")
+            value_bits = int(value_bits)
+        self.value_bits = value_bits
+        self._calls = 0
+        self._instance = next(_INSTANCES)
+        self.client_id = None  # None: client_identity() (the process's rank), as QSGDQuantCompression
         self.residual = ResidualUpdates()
         self.device = torch.device(device)
         self.compress_ratio = float(compress_ratio)
@@ -71,6 +94,20 @@ class TopKCompression(Compression):
             raise ValueError(f"tie_order must be 'torch' or 'index', not {tie_order!r}")
         self.tie_order = tie_order  # module docstring
         self._arenas = {}  # residual arenas of the batched path, per dict layout
+
+    def philox_key(self) -> int:
+        """The Philox key of this compressor's value quantiser: QSGDQuantCompression.philox_key's derivation."""
+        cid = client_identity() if self.client_id is None else int(self.client_id)
+        return philox_key(self._instance, cid)
+
+    def _next_call(self) -> int:
+        c = self._calls
+        self._calls += 1
+        return c
+
+    def residual_arena(self, names, plan):
+        """The residual arena ``encode_arena`` used for this dict layout (None before its first call)."""
+        return self._arenas.get((tuple(names), tuple(plan.sizes), str(plan.device)))
 
     def compress(self, tensor: torch.Tensor, name: str):
         """topk.py:33-42: ``((values, indices), (numel, shape))``; mutates the residual of ``name``."""

@@ -164,14 +164,17 @@ class DeviceAggregator:
         """Validate one update and stage its payloads in the device; the accumulator is not touched.
         Returns ``(q_args, t_args, adds)``: the QSGD arena ``(payload, width, level, norms, packed)`` or
         None, the Top-K selection ``(counts, values, indices)`` or None, and ``(name, tensor)`` dense terms.
-        An update's Top-K layers are all plain or all on the opt-in packed wire (``TopKBitPackedCompression``:
-        their indices are unpacked on the device as they are staged); mixed wires raise ValueError.
+        An update's Top-K layers are all plain or all on the opt-in packed index wire (``TopKBitPackedCompression``
+        and ``TopKQuantPackedCompression``, which may mix: their indices are unpacked, and the quantised values of
+        one level restored, on the device as they are staged); plain mixed with either raises ValueError.
         ``packed``: the update's QSGD layers are ``QSGDBitPackedCompression`` ones, ``payload`` is the
         packed arena (``qsgd_pack``'s layout, tensor t at byte ``offsets[t] * b / 8``) and ``width`` the
         code's bits; an update's QSGD layers are all packed or all plain."""
         from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
                                                                   _validate_layer, check_topk_indices, stage_topk)
-        from .hybrid.compression import QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME
+        from .hybrid.communicator.global_grpc_compression import QuantValues
+        from .hybrid.compression import (QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME,
+                                         TOPK_QUANT_COMPRESSION_NAME)
 
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
@@ -183,9 +186,10 @@ class DeviceAggregator:
             if got is not None:
                 topk_payload[L.layer_name] = got
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
-        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", TOPK_PACKED_COMPRESSION_NAME, "")
+        packed_topk = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
+        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", *packed_topk, "")
         qsgd = [L for L in kept if L.compression_type in known[:2]]
-        topk = [L for L in kept if L.compression_type in known[2:4]]
+        topk = [L for L in kept if L.compression_type in known[2:5]]
         dense = [L for L in kept if L.compression_type == ""]
         if any(L.compression_type not in known for L in kept):
             bad = next(L for L in kept if L.compression_type not in known)
@@ -234,9 +238,12 @@ class DeviceAggregator:
         t_args = None
         # a Top-K layer with more values than its tensor's elements repeats indices: decoded alone
         # with numpy's last-wins rule (_decode_topk_layer), as decode_updates_dict does
-        topk_packed = bool(topk) and topk[0].compression_type == TOPK_PACKED_COMPRESSION_NAME
-        if any((L.compression_type == TOPK_PACKED_COMPRESSION_NAME) != topk_packed for L in topk):
+        topk_packed = bool(topk) and topk[0].compression_type in packed_topk
+        if any((L.compression_type in packed_topk) != topk_packed for L in topk):
             raise ValueError("mixed Top-K wires (plain and bit-packed indices) within one update")
+        if len({topk_payload[L.layer_name][0].bits for L in topk
+                if isinstance(topk_payload[L.layer_name][0], QuantValues)}) > 1:
+            raise ValueError("quantised Top-K layers of different levels within one update")
         unpack_plan = self.plan if topk_packed else None  # stage_topk unpacks the indices on the device
         if topk_packed:  # the index width is the tensor size's: the layer's shape must be the plan's
             for L in topk:

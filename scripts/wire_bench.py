@@ -16,8 +16,11 @@ host round trip     : host fp32 tensors in -> LayerStates -> host fp32 tensors o
 The opt-in packed Top-K wire (TopKBitPackedCompression) has rows of its own, measured against the plain
 Top-K wire interleaved in this process (topk_packed_rows).
 
-usage: python scripts/wire_bench.py [config] [out.json] [topk_packed]
-       (a third argument "topk_packed": only the packed Top-K rows)
+The opt-in quantised value wire (TopKQuantPackedCompression, value_bits = 4) is measured the same way against
+the packed wire (topk_qval_rows).
+
+usage: python scripts/wire_bench.py [config] [out.json] [topk_packed | topk_qval]
+       (a third argument "topk_packed" / "topk_qval": only the packed / the quantised Top-K rows)
 """
 import json
 import sys
@@ -161,6 +164,53 @@ def topk_packed_rows(rounds=5):
     return out
 
 
+def topk_qval_rows(rounds=5, value_bits=4):
+    """The opt-in quantised value wire against the packed Top-K wire it rides on, interleaved as
+    topk_packed_rows: per round one 5-call median of each of encode_updates_dict and
+    decode_updates_dict(device="cuda") on both wires, packed first then quantised; reported: the median, minimum
+    and maximum over the rounds, the wire bytes, and the three value kernels alone (host-timed, launch included)."""
+    comps = {"packed": topk_comp(packed_wire=True), "quant": topk_comp(packed_wire=True, value_bits=value_bits)}
+    lay = {k: encode_updates_dict(upd, c) for k, c in comps.items()}
+    rows = {k: {"encode_updates_dict_ms": [], "decode_updates_dict_gpu_ms": []} for k in comps}
+    for _ in range(rounds):
+        for k, c in comps.items():
+            rows[k]["encode_updates_dict_ms"].append(tm(lambda: encode_updates_dict(upd, c), reps=5, warm=2))
+        for k in comps:
+            rows[k]["decode_updates_dict_gpu_ms"].append(tm(lambda: decode_updates_dict(lay[k], device=dev), reps=5, warm=2))
+    out = {"rounds": rounds, "tie_order": TK_ORDER, "value_bits": value_bits}
+    for k in comps:
+        out[k] = {m: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for m, v in rows[k].items()}
+        out[k]["values_bytes"] = sum(len(L.values_data) for L in lay[k])
+        out[k]["scale_bytes"] = sum(len(L.meta_tensor) for L in lay[k])
+        out[k]["indices_bytes"] = sum(len(L.indices_data) for L in lay[k])
+        out[k]["wire_bytes"] = sum(L.ByteSize() for L in lay[k])
+        out[k]["types"] = sorted({L.compression_type for L in lay[k]})
+    plan_p = codec.Plan.get([t.numel() for t in upd.values()], device=dev)
+    ks = plan_p.topk_ks(0.01)
+    vals = torch.randn(sum(ks), device=dev, generator=g)
+    idx = torch.cat([torch.randint(0, n, (k,), device=dev, generator=g) for n, k in zip(plan_p.sizes, ks)])
+    res_arena = torch.zeros(plan_p.arena_end, device=dev)
+    scales = plan_p.topk_value_scales(ks, vals)
+    codes = plan_p.topk_quantize_values(ks, vals, idx, scales, value_bits, 1, 2, residual=res_arena)
+    back = torch.empty_like(vals)
+    out["device_value_scales_ms"] = round(tm(lambda: plan_p.topk_value_scales(ks, vals, scales_out=scales), reps=10), 4)
+    out["device_quantize_values_ms"] = round(tm(lambda: plan_p.topk_quantize_values(
+        ks, vals, idx, scales, value_bits, 1, 2, residual=res_arena, packed_out=codes), reps=10), 4)
+    out["device_dequantize_values_ms"] = round(tm(lambda: plan_p.topk_dequantize_values(
+        ks, codes, scales, value_bits, values_out=back), reps=10), 4)
+    return out
+
+
+if len(sys.argv) > 3 and sys.argv[3] == "topk_qval":
+    progress("quantised Top-K value rows only")
+    res = {"config": cfg, "elements": N, "tensors": len(named), "copy_threads": hostio.workers(),
+           "topk_qval_wire": topk_qval_rows()}
+    print(json.dumps(res), flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    sys.exit(0)
+
 if len(sys.argv) > 3 and sys.argv[3] == "topk_packed":
     progress("packed Top-K rows only")
     res = {"config": cfg, "elements": N, "tensors": len(named), "copy_threads": hostio.workers(),
@@ -275,6 +325,8 @@ res["device_decode_packed_ms"] = round(tm(lambda: plan.qsgd_decode_packed(pk, 16
 res["device_decode_int8_ms"] = round(tm(lambda: plan.qsgd_decode(qq, 8, 16, nn, y_out=avg), reps=10), 4)
 progress("packed Top-K rows")
 res["topk_packed_wire"] = topk_packed_rows()
+progress("quantised Top-K value rows")
+res["topk_qval_wire"] = topk_qval_rows()
 line = json.dumps(res)
 print(line, flush=True)
 if out_path:
