@@ -19,8 +19,8 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libomf_codec.so")
 
 SOURCES = ["omf_runtime.cpp", "omf_plan_layout.cpp", "omf_qsgd.hip", "omf_qsgd_recv.hip", "omf_qsgd_bracket.hip",
-           "omf_qsgd_ring.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_recv.hip", "omf_topk_tie.hip",
-           "omf_topk_pack.hip", "omf_topk_qval.hip", "omf_topk_host.cpp", "omf_topk_layout.cpp"]
+           "omf_qsgd_ring.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_sampled.hip", "omf_topk_exact.hip",
+           "omf_topk_recv.hip", "omf_topk_tie.hip", "omf_topk_pack.hip", "omf_topk_qval.hip", "omf_topk_host.cpp", "omf_topk_layout.cpp"]
 
 # Exact IEEE fp32 (no contraction, denormals kept, correctly rounded / and sqrt): the
 # payload must match the reference bit for bit.

@@ -20,13 +20,13 @@ constexpr unsigned kOrderEventFlags = hipEventDisableTiming | hipEventDisableSys
 
 // Top-K encoder counters of a plan (omf_topk_stats) that the host knows: calls of the sampled
 // path and of the exact path.  Which path a sampled call took (bucket-sort fast path, zero fill,
-// the exact tail's fallback, a redo) is decided on the device, which counts it (omf_topk.hip).
+// the exact tail's fallback, a redo) is decided on the device, which counts it (topk_exact_tail, omf_topk_exact.hip).
 struct TopkStats {
   int64_t calls = 0, exact = 0;
 };
 
-// Top-K encoder settings of a plan (omf_topk.hip): in experiment builds read from the OMF_TOPK_* environment once, at
-// the plan's first Top-K call, and settable by the omf_plan_set_topk test / experiment hook.
+// Top-K encoder settings of a plan (omf_topk.hip; its units' launchers use them): in experiment builds read from the
+// OMF_TOPK_* environment once, at the plan's first Top-K call, and settable by the omf_plan_set_topk test hook.
 struct TopkKnobs {
   TopkStats stats;
   bool init = false;

@@ -3,10 +3,11 @@
 // Not part of the C ABI.  omf_qsgd.hip creates, uploads and destroys a plan and launches the QSGD
 // encoders from it (the bracketed encoder's: omf_qsgd_bracket.hip, which also makes that encoder's lazy
 // buffers); omf_qsgd_recv.hip (the decoders and the K-client sum), omf_qsgd_pack.hip (the packed wire) and
-// the Top-K units (omf_topk.hip the encoder, omf_topk_recv.hip decode and checks, omf_topk_tie.hip the tie
-// rewrite) read its arena tables; the Top-K units keep their per-plan device tables in it.  The host tables come from omf_plan_layout.h; Top-K's host state
-// (its workspace layout, made at the plan's first Top-K use, and its latest encode tables) is
-// omf_topk_layout.h's.
+// the Top-K units (omf_topk.hip the encoder's host side, omf_topk_sampled.hip and omf_topk_exact.hip its
+// kernels and launches, omf_topk_recv.hip decode and checks, omf_topk_tie.hip the tie rewrite) read its arena
+// tables; the Top-K units keep their per-plan device tables in it.  The host tables come from omf_plan_layout.h;
+// Top-K's host state (its workspace layout, made at the plan's first Top-K use, and its latest encode tables)
+// is omf_topk_layout.h's.
 #pragma once
 
 #include <algorithm>

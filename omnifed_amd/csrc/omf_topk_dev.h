@@ -1,4 +1,4 @@
-// omf_topk_dev.h — the device steps the exact tail (omf_topk.hip), the receive kernels (omf_topk_recv.hip), the
+// omf_topk_dev.h — the device steps the exact tail (omf_topk_exact.hip), the receive kernels (omf_topk_recv.hip), the
 // index pack (omf_topk_pack.hip) and the value quantiser (omf_topk_qval.hip) share.
 #pragma once
 #include <stdint.h>

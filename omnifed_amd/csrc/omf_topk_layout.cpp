@@ -138,7 +138,6 @@ EncodeWsLayout encode_ws_layout(const std::vector<int64_t>& sizes, int64_t arena
   OMF_REGION(c, EncodeWs, fcount, nt);
   OMF_REGION(c, EncodeWs, fhist, nt * kFineMax);
   OMF_REGION(c, EncodeWs, fbucket, nt * kFineMax);
-  OMF_REGION(c, EncodeWs, fse, nt * kFineMax);
   OMF_REGION(c, EncodeWs, bstart, nb_max);    // the bucket tables: sum of bucket_slots(n_t)
   OMF_REGION(c, EncodeWs, brec, nb_max);
   OMF_REGION(c, EncodeWs, bfill, nb_max);

@@ -6,9 +6,9 @@
 // the packed arena's tables) with the quantised-value wire's layout rule beside it.
 //
 // Pure integer code: no HIP header, so tests/host/topk_layout_check.cpp runs it on a CPU under
-// sanitizers.  omf_topk.hip (the encoder) and omf_topk_recv.hip (decode and checks) upload what the
-// builders return, bind their pointers with the carves declared here and call the same rule functions
-// from their kernels.
+// sanitizers.  omf_topk.hip (the encoder's host side) and omf_topk_recv.hip (decode and checks) upload what
+// the builders return and bind their pointers with the carves declared here; the encoder's kernels
+// (omf_topk_sampled.hip, omf_topk_exact.hip) and the receive kernels call the same rule functions.
 #pragma once
 
 #include <algorithm>
@@ -201,7 +201,7 @@ struct EncodeWs {
   uint64_t *cand, *sorted;
   uint32_t *fmap, *tlo, *thi, *fcount, *fhist;
   int32_t* fbucket;
-  uint32_t *fse, *bstart;
+  uint32_t* bstart;
   BucketRec* brec;
   uint32_t* bfill;
   unsigned char* tmp;

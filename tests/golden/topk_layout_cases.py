@@ -26,9 +26,11 @@ def a256(b):
 
 
 def dead_bytes(nt):
-    """The seven workspace regions the encoder stopped allocating (koff, kk, kb2, tfirst, tlast, bbase,
-    sbase: their contents are in the plan-owned table), as the recorded build laid them out."""
-    return a256(8 * (nt + 1)) + 2 * a256(8 * nt) + 2 * a256(4 * nt) + 2 * a256(4 * (nt + 1))
+    """The eight workspace regions the encoder stopped allocating, as the recorded build laid them out: koff,
+    kk, kb2, tfirst, tlast, bbase and sbase (their contents are in the plan-owned table), and fse (16384 fine
+    bins of 4 bytes per tensor, a table topk_plan stored and nothing read)."""
+    tables = a256(8 * (nt + 1)) + 2 * a256(8 * nt) + 2 * a256(4 * nt) + 2 * a256(4 * (nt + 1))
+    return tables + a256(4 * nt * 16384)
 
 
 # Two plans of equal nt and arena_end and different sizes (explicit offsets): 152 against 40 bucket slots,

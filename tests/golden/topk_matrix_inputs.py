@@ -112,7 +112,7 @@ def _fmix32(h):
 
 
 def _sample_positions(n, t, max_runs):
-    """The elements omf_topk.hip's topk_sample reads for tensor t: one aligned run of 16 per
+    """The elements omf_topk_sampled.hip's topk_sample reads for tensor t: one aligned run of 16 per
     max(256, ceil(n / max_runs)) elements, at a hashed position."""
     stride = max(256, -(-n // max_runs))
     lo = np.arange(0, n, stride, dtype=np.uint64)

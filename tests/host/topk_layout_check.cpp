@@ -221,7 +221,7 @@ static EncodeWsLayout check_ws(const Arena& a) {
       {"sub_cnt", 4 * items * (size_t)kSubsPerItem}, {"item_cnt", 4 * items}, {"item_off", 4 * items},
       {"cand", 8 * ae}, {"sorted", 8 * (ae + nt * (size_t)kBucketPad)}, {"fmap", 4 * nt * (size_t)kCoarse},
       {"tlo", 4 * nt}, {"thi", 4 * nt}, {"fcount", 4 * nt}, {"fhist", 4 * nt * (size_t)kFineMax},
-      {"fbucket", 4 * nt * (size_t)kFineMax}, {"fse", 4 * nt * (size_t)kFineMax}, {"bstart", 4 * slots},
+      {"fbucket", 4 * nt * (size_t)kFineMax}, {"bstart", 4 * slots},
       {"brec", sizeof(BucketRec) * slots}, {"bfill", 4 * slots}, {"tmp", a.tmp_bytes}};
   CHECK(L.carve.regions().size() == need.size());
   check_carve(L.carve);

@@ -4,7 +4,7 @@ The reference PS serves SendUpdate / GetUpdatedModel from ``grpc.server(ThreadPo
 max_workers=10))`` (global_grpc.py:44-45): each request runs on whichever worker is free, under
 the servicer's ``self.lock`` (global_grpc_server.py:78, 181, 198); a client and the PS may also
 share a process.  Per-thread state the codec meets there: torch's current stream and device,
-the Top-K encoder's per-thread verdict word (omf_topk.hip), and the pinned staging buffers
+the Top-K encoder's per-thread stream state (HostSync, omf_topk_sampled.hip), and the pinned staging buffers
 (omnifed_amd.hostio: leased per call).  Both tests compare bytes with a single-thread run.
 """
 

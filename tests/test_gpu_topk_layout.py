@@ -6,14 +6,14 @@ build) holds, for the four plans of tests/golden/topk_matrix_inputs.py at their 
 and decode-by-counts workspace sizes, and the encode sizes of the two plans below.
 
 Part one (no kernel is launched): the decode sizes are the recorded ones exactly; the encode size is the
-recorded one minus the seven regions the encoder no longer allocates (koff, kk, kb2, tfirst, tlast, bbase,
-sbase: ``topk_layout_cases.dead_bytes``, read off the recorded build's layout and checked against the
-fixture when it was made).
+recorded one minus the eight regions the encoder no longer allocates (koff, kk, kb2, tfirst, tlast, bbase,
+sbase, and the unread fse table: ``topk_layout_cases.dead_bytes``, read off the recorded build's layout and
+checked against the fixture when it was made).
 
 Part two: two plans of equal nt and arena_end and different sizes — 152 against 40 bucket slots, so
 different bucket-table regions (tests/host/topk_layout_check.cpp asserts that they differ) — are made,
 used for one mode-0 encode and destroyed in turn on one thread.  Each must report its own size (its recorded fresh-process size minus the
-seven regions; the recorded build's cache, keyed by the plan's address, nt and arena_end, could hand a
+eight regions; the recorded build's cache, keyed by the plan's address, nt and arena_end, could hand a
 plan the other's) and select what the oracle (``oracle.topk_ef_step``, mode 0) selects, byte for byte.
 """
 

@@ -7,7 +7,7 @@ its own (n = 1, sizes around 512 and 16384, two super-items, ratio 1.0, 257 tens
 64 / 2048 / 2^20, 1 to nt + 3 groups) and asserts what the kernels rely on, under AddressSanitizer and
 UBSan; the flat-item ranges are held to omf_plan_layout.cpp's tables.  For the plans of the sampled path
 the workspace total is also held to the size an MI355X build recorded before the encoder stopped
-allocating seven regions (tests/golden/topk_layout_parent.npz, the fixture of
+allocating eight regions (tests/golden/topk_layout_parent.npz, the fixture of
 tests/test_gpu_topk_layout.py): the recorded size minus those regions.
 """
 
