@@ -11,7 +11,8 @@
  *
  * Conventions
  *  - Every pointer argument is DEVICE memory owned by the caller unless noted.
- *    The library allocates only in omf_plan_create (its own workspace) and, once per
+ *    The library allocates only in omf_plan_create (its own workspace), omf_host_alloc
+ *    (the caller's page-locked host memory) and, once per
  *    (plan, Top-K ratio), a small constant table on the first Top-K call at that ratio
  *    (synchronous, not on the hot path after that).  The hot-path calls never allocate or
  *    copy host memory, and never synchronise — except omf_topk_torch_order (host work on
@@ -64,11 +65,23 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 116
+#define OMF_ABI_VERSION 117
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
 const char* omf_last_error(void);
+
+/*
+ * Page-locked HOST memory (hipHostMalloc) for the Python layer's opt-in pinned result arenas
+ * (hostio.PINNED_ARENAS: the CPU placement of decode_updates_dict,
+ * global_grpc_compression.py:214-223, landing by one DMA): *out receives nbytes > 0 bytes that
+ * the current device copies into and out of asynchronously.  Synchronous, not a hot-path call.
+ * OMF_ENOMEM when the host cannot lock that much; OMF_EHIP without a device; *out is NULL on
+ * every failure, and no HIP error is left pending.  omf_host_free(NULL) does nothing; freeing
+ * waits for the device, so no copy is in flight into memory that goes back to the OS.
+ */
+int omf_host_alloc(size_t nbytes, void** out);
+int omf_host_free(void* ptr);
 
 /*
  * Plan over a fixed list of named tensors (one client's update dict).

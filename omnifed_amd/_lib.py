@@ -33,6 +33,8 @@ _c_size = ctypes.c_size_t
 SIGNATURES = {
     "omf_abi_version": (ctypes.c_int, []),
     "omf_last_error": (ctypes.c_char_p, []),
+    "omf_host_alloc": (ctypes.c_int, [_c_size, ctypes.POINTER(_c_p)]),
+    "omf_host_free": (ctypes.c_int, [_c_p]),
     "omf_plan_create": (ctypes.c_int, [ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i32, _c_i64,
                                         ctypes.c_int, ctypes.POINTER(_c_p)]),
     "omf_plan_destroy": (ctypes.c_int, [_c_p]),
@@ -105,7 +107,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 116 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 117 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

@@ -36,6 +36,8 @@ from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _lib
+
 CHUNK_BYTES = 32 << 20
 INLINE_BYTES = 1 << 20  # a copy this small is done on the calling thread (a pool hand-off costs more)
 
@@ -272,19 +274,20 @@ class _HostLease:
         self.pool._returned.append(self.mem)  # list.append is atomic: no lock in a finaliser
 
 
-def _register(ptr: int, nbytes: int) -> bool:
-    """Page-lock host memory in place (hipHostRegister through torch's runtime binding)."""
-    try:
-        return int(torch._C._cudart.cudaHostRegister(ptr, nbytes, 0)) == 0
-    except Exception:  # pragma: no cover - no HIP runtime
-        return False
+def _alloc_pinned(nbytes: int):
+    """``nbytes`` of page-locked host memory (hipHostMalloc through the codec library) as a numpy
+    uint8 array that does not own it, or None where it cannot be had (no device, or the host will
+    not lock that much)."""
+    import numpy as np
+
+    ptr = ctypes.c_void_p()
+    if _lib.lib().omf_host_alloc(nbytes, ctypes.byref(ptr)) != _lib.OMF_OK:
+        return None
+    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(nbytes,))
 
 
-def _unregister(ptr: int) -> None:
-    try:
-        torch._C._cudart.cudaHostUnregister(ptr)
-    except Exception:  # pragma: no cover
-        pass
+def _free_pinned(ptr: int) -> None:
+    _lib.check(_lib.lib().omf_host_free(ptr), "omf_host_free")
 
 
 def _pin_budget_from_env() -> int:
@@ -306,12 +309,12 @@ class HostArenaPool:
     handed out are ordinary, writable CPU tensors (numpy-backed storage); the pool keeps at most
     ``max_bytes`` of free buffers (the rest goes back to the OS).
 
-    ``pinned``: the buffers are page-locked in place (hipHostRegister on numpy memory), so a DMA
+    ``pinned``: the buffers are allocated page-locked (``_alloc_pinned``), so a DMA
     lands in them directly — opt-in (``OMF_PIN_HOST_ARENAS`` / ``set_pinned_arenas``), because
     page-locking gigabytes on a PS host is a resource-policy change the reference never makes.
     Every page-locked byte, handed out or pooled, counts against ``max_bytes``: ``empty`` returns
     None when a new buffer would exceed it (the caller then takes the pageable path), and a buffer
-    trimmed from the pool is unregistered before its memory goes back to the OS."""
+    trimmed from the pool is freed, its memory going back to the OS unlocked."""
 
     GRAIN = 64 << 20      # sizes rounded up to this above it (to 1 MiB below)
     MIN_BYTES = 1 << 20   # smaller arenas are not pooled
@@ -329,7 +332,7 @@ class HostArenaPool:
 
     def _release(self, m) -> None:
         if self.pinned:
-            _unregister(m.ctypes.data)
+            _free_pinned(m.ctypes.data)
             self.live_bytes -= _nbytes(m)
 
     def _drain(self) -> None:
@@ -368,10 +371,10 @@ class HostArenaPool:
                         self._release(self._free.pop())
                     if self.live_bytes + size > self.max_bytes:
                         return None
-                mem = self._np.empty(size, dtype=self._np.uint8)
+                mem = _alloc_pinned(size) if self.pinned else self._np.empty(size, dtype=self._np.uint8)
+                if mem is None:
+                    return None
                 if self.pinned:
-                    if not _register(mem.ctypes.data, size):
-                        return None
                     self.live_bytes += size
         return torch.from_numpy(self._np.asarray(_HostLease(mem, nbytes, self)))
 

@@ -234,7 +234,7 @@ def test_pinned_arena_pool_tensors_are_page_locked(gpu):
     """Page-locked arenas are opt-in and bounded (round 5): the product pool has no budget unless
     OMF_PIN_HOST_ARENAS gives it one; a pinned pool's tensors are seen by torch as pinned (the
     copies into them are asynchronous DMAs); every page-locked byte, handed out or free, counts
-    against the budget (a request beyond it gets None); a trimmed buffer is unregistered."""
+    against the budget (a request beyond it gets None); a trimmed buffer is freed."""
     import gc
     import os
 
@@ -259,7 +259,7 @@ def test_pinned_arena_pool_tensors_are_page_locked(gpu):
     assert w is not None and P.live_bytes == 8 * MiB
     del t, w
     gc.collect()
-    P.set_max_bytes(0)  # trims every free buffer: unregistered, memory released
+    P.set_max_bytes(0)  # trims every free buffer: its page-locked memory released
     assert P.free_bytes() == 0 and P.live_bytes == 0
 
 

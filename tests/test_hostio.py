@@ -84,8 +84,14 @@ def test_pinned_leases_returned_after_the_budget_is_removed_are_released(monkeyp
     from omnifed_amd import hostio
 
     locked = {}
-    monkeypatch.setattr(hostio, "_register", lambda ptr, n: locked.__setitem__(ptr, n) or True)
-    monkeypatch.setattr(hostio, "_unregister", lambda ptr: locked.pop(ptr))
+
+    def alloc(n):  # stands in for the page-locked allocation: no device here
+        mem = np.empty(n, np.uint8)
+        locked[mem.ctypes.data] = mem
+        return mem
+
+    monkeypatch.setattr(hostio, "_alloc_pinned", alloc)
+    monkeypatch.setattr(hostio, "_free_pinned", lambda ptr: locked.pop(ptr))
     pool = hostio.HostArenaPool(max_bytes=0, pinned=True)
     monkeypatch.setattr(hostio, "PINNED_ARENAS", pool)
     hostio.set_pinned_arenas(64 << 20)
