@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 117
+#define OMF_ABI_VERSION 118
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -131,8 +131,8 @@ int omf_plan_set_encode_strategy(omf_plan* plan, int32_t strategy);
  * encoder (1). */
 int32_t omf_plan_encode_strategy(const omf_plan* plan);
 /* The encoder the plan's latest encode (or fused PS step) launched: 0 register-resident +
- * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in);
- * -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in),
+ * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -178,6 +178,24 @@ int omf_qsgd_encode_ex(omf_plan* plan, const float* x, float alpha, int32_t bit_
                        float* norm_out, void* stream);
 int omf_qsgd_norms_ex(omf_plan* plan, const float* x, float alpha, int32_t value_format, float* norm_out,
                       void* stream);
+
+/*
+ * omf_qsgd_encode_ex / omf_qsgd_norms_ex without the fp32 upcast: x16 is an arena of 16-bit elements, the
+ * tensors' own bf16 (value_format 1) or fp16 (2) bit patterns, tensor t at x16[offsets[t] .. + sizes[t])
+ * in ELEMENTS of the plan's offsets; 16-byte aligned, arena_end elements long.  Nothing outside the
+ * tensors' ranges is read.  Everything else (u, seed / offset and the Philox slots, norm_in, the payload
+ * arena, norm_out, the roundings of omf_qsgd_encode_ex) is as there, and so are the results: the norm is
+ * the two-pass encoder's (strategy 1) on the exact upcast bit for bit, the payload every encoder's given
+ * that norm.  Two launches on `stream`: the tensors' sums of squares and their fold to the norms (skipped
+ * with norm_in), then the levels; 5 bytes of memory traffic per element on the int8 wire against 11
+ * through an upcast arena.  No host allocation, no in-kernel wait (omf_plan_check has nothing to report
+ * for it).
+ */
+int omf_qsgd_encode_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, int32_t bit_width,
+                        const float* u, uint64_t seed, uint64_t offset, const float* norm_in, void* q_out,
+                        float* norm_out, void* stream);
+int omf_qsgd_norms_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, float* norm_out,
+                       void* stream);
 
 /*
  * Fused PS step: avg_out = acc / divisor (IEEE fp32 division, as the reference's

@@ -57,6 +57,12 @@ int omf_plan_set_wide_levels(omf_plan* plan, int32_t on);
  * without a fused last client: bit_width 1-4, and 5-8 when wide levels are on (one-wave workgroups); identical
  * payloads either way. */
 int omf_plan_set_fused_bracket(omf_plan* plan, int32_t on);
+/* The 16-bit-arena encoder's load shape and block size (omf_qsgd_encode_h16; scripts/h16_encode_ab.py times
+ * them): wide_loads 0 = 8-byte loads (the default: measured faster), 1 = 16-byte loads with the lane-pair
+ * swap (served where every offset is a multiple of 8 elements, else the 8-byte loads run); rows = 4 (default)
+ * or 8 rows of 1024 elements per quantise workgroup.  A negative argument keeps the setting.  Identical
+ * norms and payloads either way. */
+int omf_plan_set_h16(omf_plan* plan, int32_t wide_loads, int32_t rows);
 /* Diagnostics of the last bracketed single-read encode (strategy 3; synchronises `stream`,
  * not for the hot path): out[0] tensors requantised whole (norm outside the sampled bracket,
  * a wave's undecided-quad slot overflowed, or a degenerate sample), out[1] of those the

@@ -57,6 +57,10 @@ SIGNATURES = {
     "omf_qsgd_encode_ex": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_i32, _c_i32, _c_p, _c_u64, _c_u64, _c_p, _c_p, _c_p,
                                           _c_p]),
     "omf_qsgd_norms_ex": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_i32, _c_p, _c_p]),
+    "omf_qsgd_encode_h16": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_f32, _c_i32, _c_p, _c_u64, _c_u64, _c_p, _c_p, _c_p,
+                                           _c_p]),
+    "omf_qsgd_norms_h16": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_f32, _c_p, _c_p]),
+    "omf_plan_set_h16": (ctypes.c_int, [_c_p, _c_i32, _c_i32]),
     "omf_ps_apply_encode": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_p, _c_i32, _c_p, _c_u64, _c_u64, _c_p, _c_p,
                                            _c_p]),
     "omf_ps_accumulate_apply_encode": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_f32, _c_p,
@@ -107,7 +111,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 117 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 118 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

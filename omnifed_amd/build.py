@@ -19,7 +19,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libomf_codec.so")
 
 SOURCES = ["omf_runtime.cpp", "omf_plan_layout.cpp", "omf_qsgd.hip", "omf_qsgd_recv.hip", "omf_qsgd_bracket.hip",
-           "omf_qsgd_ring.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_sampled.hip", "omf_topk_exact.hip",
+           "omf_qsgd_ring.hip", "omf_qsgd_h16.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_sampled.hip", "omf_topk_exact.hip",
            "omf_topk_recv.hip", "omf_topk_tie.hip", "omf_topk_pack.hip", "omf_topk_qval.hip", "omf_topk_host.cpp", "omf_topk_layout.cpp"]
 
 # Exact IEEE fp32 (no contraction, denormals kept, correctly rounded / and sqrt): the
@@ -35,6 +35,10 @@ FLAGS = [
     "-Wall",
     "-Wno-unused-function",
 ]
+
+# Per-unit additions.  The 16-bit-arena encoder is compiled without packed fp32 instructions: its pair
+# divisions (omf_qsgd_dev.h) become two scalar fmas each, the same IEEE results.
+UNIT_FLAGS = {"omf_qsgd_h16.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc() -> str:
@@ -74,7 +78,8 @@ def needs_build() -> bool:
 
 def _toolchain_stamp() -> str:
     """The compiler and flags the objects in _obj were built with."""
-    return "\n".join([os.path.realpath(hipcc()), *FLAGS]) + "\n"
+    units = [f"{u}: {' '.join(f)}" for u, f in sorted(UNIT_FLAGS.items())]
+    return "\n".join([os.path.realpath(hipcc()), *FLAGS, *units]) + "\n"
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -101,7 +106,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
         if not force and os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in [src, *headers]):
             continue  # object newer than its source and every header
-        cmd = [hipcc(), *FLAGS, "-I", INCLUDE, "-c", src, "-o", obj]
+        cmd = [hipcc(), *FLAGS, *UNIT_FLAGS.get(os.path.basename(src), []), "-I", INCLUDE, "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), src))

@@ -107,6 +107,20 @@ def _need(t: torch.Tensor, name: str, dtype, device, numel: int, align: int):
 # encoder strategies by omf_plan_set_encode_strategy code (include/omf_codec.h)
 STRATEGIES = ("resident", "ordered", "ring", "bracket", "grid")
 
+# 16-bit arena dtypes and the value format each implies (omf_qsgd_encode_h16)
+H16_FORMATS = {torch.bfloat16: 1, torch.float16: 2}
+
+
+def _h16_format(x: torch.Tensor, value_format: int) -> int:
+    """The value format of a call on arena ``x``: for a bf16 / fp16 arena the dtype's own (an explicit
+    ``value_format`` that contradicts it raises ``ValueError``), else ``value_format``."""
+    fmt = H16_FORMATS.get(getattr(x, "dtype", None))
+    if fmt is None:
+        return int(value_format)
+    if int(value_format) not in (0, fmt):
+        raise ValueError(f"x: dtype {x.dtype} implies value_format {fmt}, not {int(value_format)}")
+    return fmt
+
 
 DECODE_BLOCK = 4096  # elements per decode block (omf_qsgd_decode_range granularity)
 
@@ -253,9 +267,9 @@ class Plan:
     @property
     def last_encoder(self) -> str:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
-        "norm_in" (levels with caller norms) or "none"."""
+        "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
-        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else ("norm_in" if code == 5 else "none")
+        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {5: "norm_in", 6: "h16"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -267,7 +281,7 @@ class Plan:
         """The kernel name (or "qsgd_spec_all" for the bracketed encoder's three launches) of the
         latest encode — what a profile of it shows."""
         return {"bracket": "qsgd_spec_all", "ring": "qsgd_encode_pc", "grid": "qsgd_encode_grid",
-                "norm_in": "qsgd_quant_sub"}.get(self.last_encoder, "qsgd_encode_ordered")
+                "norm_in": "qsgd_quant_sub", "h16": "qsgd_h16_quant"}.get(self.last_encoder, "qsgd_encode_ordered")
 
     def encoder_kernel_for(self, bit_width: int) -> str:
         """The kernel an fp32, on-device-draw encode at ``bit_width`` runs by default: the bracketed
@@ -278,6 +292,13 @@ class Plan:
             return "qsgd_encode_pc" if storage_width(2 ** int(bit_width)) == 32 else "qsgd_encode_ordered"
         return {"ring": "qsgd_encode_pc", "bracket": "qsgd_spec_all", "grid": "qsgd_encode_grid"}.get(
             self.strategy, "qsgd_encode_ordered")
+
+    def set_h16(self, wide_loads: int = -1, rows: int = -1) -> None:
+        """Experiment hook of the 16-bit-arena encoder (omf_plan_set_h16): 8-byte loads (0, the default) or
+        16-byte loads with the lane-pair swap (1); 4 (default) or 8 rows per quantise workgroup.  Identical
+        results."""
+        with self._lock:
+            check(lib().omf_plan_set_h16(self._h, int(wide_loads), int(rows)), "omf_plan_set_h16")
 
     def set_ring(self, cfg: int = -1, big_mode: int = -1, gap: int = -2, hold_max: int = -1) -> None:
         """Tuning / test hook of the ring encoder: see omf_plan_set_ring."""
@@ -321,14 +342,18 @@ class Plan:
         """Encode the whole arena ``x``; returns ``(q, norms)`` (device tensors).
 
         ``value_format``: 0 fp32, 1 bf16, 2 fp16 — the dtype the tensors had (x holds their exact
-        fp32 upcast; omf_qsgd_encode_ex rounds where the reference's reduced-precision ops do)."""
+        fp32 upcast; omf_qsgd_encode_ex rounds where the reference's reduced-precision ops do).
+        A bf16 / fp16 ``x`` is the tensors' own 16-bit arena (the plan's offsets, in elements): no
+        upcast, its dtype is the value format (omf_qsgd_encode_h16; the same norms and payload)."""
+        fmt = _h16_format(x, value_format)
+        h16 = getattr(x, "dtype", None) in H16_FORMATS
         s = int(bit_width)
         if not 0 <= s <= 30:
             raise ValueError("bit_width must be in [0, 30]")
         width = storage_width(2 ** s)
         qdt = torch.int8 if width == 8 else torch.int32
         dev = self.device
-        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        _need(x, "x", x.dtype if h16 else torch.float32, dev, self.arena_end, 16)
         if q_out is None:
             q_out = torch.empty(self.payload_elems(width), dtype=qdt, device=dev)
         _need(q_out, "q_out", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
@@ -340,11 +365,16 @@ class Plan:
         if norm_in is not None:
             _need(norm_in, "norm_in", torch.float32, dev, self.nt, 4)
         st = stream if stream is not None else _stream(dev)
+        seed, offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF
         with self._lock:
-            check(lib().omf_qsgd_encode_ex(self._h, _ptr(x), float(alpha), s, int(value_format), _ptr(u),
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
-                                           _ptr(norm_in), _ptr(q_out), _ptr(norm_out), ctypes.c_void_p(st)),
-                  "omf_qsgd_encode_ex")
+            if h16:
+                check(lib().omf_qsgd_encode_h16(self._h, _ptr(x), fmt, float(alpha), s, _ptr(u), seed, offset,
+                                                _ptr(norm_in), _ptr(q_out), _ptr(norm_out), ctypes.c_void_p(st)),
+                      "omf_qsgd_encode_h16")
+            else:
+                check(lib().omf_qsgd_encode_ex(self._h, _ptr(x), float(alpha), s, fmt, _ptr(u), seed, offset,
+                                               _ptr(norm_in), _ptr(q_out), _ptr(norm_out), ctypes.c_void_p(st)),
+                      "omf_qsgd_encode_ex")
         return q_out, norm_out
 
     def ps_apply_encode(self, acc: torch.Tensor, divisor: float, bit_width: int,
@@ -428,15 +458,22 @@ class Plan:
 
     def qsgd_norms(self, x: torch.Tensor, alpha: float = 1.0, norm_out: Optional[torch.Tensor] = None,
                    stream: Optional[int] = None, value_format: int = 0) -> torch.Tensor:
+        """The tensors' norms alone; ``x`` and ``value_format`` as for ``qsgd_encode``."""
         dev = self.device
-        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        fmt = _h16_format(x, value_format)
+        h16 = getattr(x, "dtype", None) in H16_FORMATS
+        _need(x, "x", x.dtype if h16 else torch.float32, dev, self.arena_end, 16)
         if norm_out is None:
             norm_out = torch.empty(self.nt, dtype=torch.float32, device=dev)
         _need(norm_out, "norm_out", torch.float32, dev, self.nt, 4)
         st = stream if stream is not None else _stream(dev)
         with self._lock:
-            check(lib().omf_qsgd_norms_ex(self._h, _ptr(x), float(alpha), int(value_format), _ptr(norm_out),
-                                          ctypes.c_void_p(st)), "omf_qsgd_norms_ex")
+            if h16:
+                check(lib().omf_qsgd_norms_h16(self._h, _ptr(x), fmt, float(alpha), _ptr(norm_out),
+                                               ctypes.c_void_p(st)), "omf_qsgd_norms_h16")
+            else:
+                check(lib().omf_qsgd_norms_ex(self._h, _ptr(x), float(alpha), fmt, _ptr(norm_out),
+                                              ctypes.c_void_p(st)), "omf_qsgd_norms_ex")
         return norm_out
 
     def qsgd_decode(self, q: torch.Tensor, width: int, levels: int, norm: torch.Tensor,

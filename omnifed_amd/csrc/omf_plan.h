@@ -47,6 +47,12 @@ struct omf_plan {
   uint32_t epoch = 0;            // last granule tag used (host-side launch counter)
   int32_t ev = 8;                // encode rows per thread (sub-chunk = ev * 1024 elements): 8 measured
                                  // faster than 16 for the two-pass encoder (0.596 vs 0.606 ms, Llama-400M)
+  // 16-bit arenas (omf_qsgd_h16.hip): 8-byte loads and 4 rows of 1024 elements per quantise block, the
+  // measured choice (profiles/h16_encode_ab.json: Llama-400M bf16 0.467 ms against 0.485 with 8 rows, and
+  // 0.477 / 0.509 with the 16-byte loads and their pair swap); omf_plan_set_h16 asks for the 16-byte loads,
+  // served where every tensor starts on a 16-byte boundary of such an arena
+  int32_t h16_wide = 0, h16_rows = 4;
+  bool h16_aligned = false;
   // ---- the plan's block: one device allocation, carved by upload_plan (omf_qsgd.hip) in this order
   void* d_block = nullptr;
   uint8_t* d_sync = nullptr;    // [ticket u32, err u32, pad 8][counters u32 x nt, pad16][granules u64 x nt, pad16]

@@ -5,8 +5,9 @@
 //
 // Kernel map (the bracketed single-read encoder, strategy 3, is omf_qsgd_bracket.hip
 // and the single-read ring encoder omf_qsgd_ring.hip; the device steps the encoders share are
-// omf_qsgd_enc.h; the decoders, the K-client sum and the flat divide are omf_qsgd_recv.hip).  Every
-// encoder writes the same payload bits for the same norm.
+// omf_qsgd_enc.h; the decoders, the K-client sum and the flat divide are omf_qsgd_recv.hip; bf16 / fp16
+// tensors in a 16-bit arena are encoded by omf_qsgd_h16.hip, behind omf_qsgd_encode_h16 at the end of this
+// file).  Every encoder writes the same payload bits for the same norm.
 //   qsgd_encode_ordered    ticket-ordered encoder (strategies 0 and 1, and every norms-only pass): one
 //                          launch for every tensor.  Work items are taken in ticket order (an atomic
 //                          counter, so a workgroup only waits on items that are already running):
@@ -37,6 +38,7 @@
 #include "../../include/omf_codec_experimental.h"
 #include "omf_bracket.h"
 #include "omf_common.h"
+#include "omf_h16.h"
 #include "omf_plan.h"
 #include "omf_qsgd_dec.h"
 #include "omf_qsgd_enc.h"
@@ -66,41 +68,6 @@ __device__ __forceinline__ float chunk_sumsq(const EncArgs& a, int64_t b, int64_
     acc = sumsq_f4<V>(v, acc);
   }
   return acc;
-}
-
-struct HandoffShared {
-  double red[kWaves];
-  uint32_t last, ok;
-  float norm;
-};
-
-// Publish one item's partial; the last arriver of the tensor folds all partials in a fixed
-// order (deterministic norm) and publishes the {tag = 1, norm} granule.  Protocol
-// (cdna_hip_programming.md §6 G16): partial stored sc1 and drained before the
-// agent-scope counter add; the last arriver reads the partials with sc1 loads.
-__device__ __forceinline__ void publish_partial(const EncArgs& a, const TensorInfo& ti, int32_t t, int32_t idx,
-                                                float acc, HandoffShared& sh) {
-  const double s = block_sum_f64((double)acc, sh.red);
-  if (threadIdx.x == 0) {
-    st_agent(&a.partials[ti.pbase + idx], (uint64_t)__double_as_longlong(s));
-    drain_vmem();
-    const uint32_t old = add_agent(&a.counters[t], 1u);
-    sh.last = (old == (uint32_t)(ti.nchunks - 1)) ? 1u : 0u;
-    // Every partial of t has arrived: reset the counter for the next launch (stream order).
-    if (sh.last) __hip_atomic_store(&a.counters[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (sh.last) {
-    double p = 0.0;
-    for (int j = threadIdx.x; j < ti.nchunks; j += kThreads)
-      p += __longlong_as_double((long long)ld_agent(&a.partials[ti.pbase + j]));
-    const double tot = block_sum_f64(p, sh.red);
-    if (threadIdx.x == 0) {
-      const float norm = finish_norm(tot, a.fmt);
-      a.norm_out[t] = norm;
-      st_agent(&a.gran[t], ((uint64_t)a.epoch << 32) | (uint64_t)__float_as_uint(norm));
-    }
-  }
 }
 
 // Poll the tensor's granule (one lane, relaxed sc1 loads, bounded).  On timeout (the
@@ -580,6 +547,7 @@ int omf_plan_create(const int64_t* sizes, const int64_t* offsets, int32_t ntenso
   p->sizes.assign(sizes, sizes + ntensors);
   p->offsets.assign(offsets, offsets + ntensors);
   p->arena_end = offsets[ntensors - 1] + sizes[ntensors - 1];
+  p->h16_aligned = std::all_of(offsets, offsets + ntensors, [](int64_t o) { return (o & 7) == 0; });
   p->spec_last_pw = kSpecPerWave;
   {
     // Co-resident capacity of the encoder (occupancy x CUs over every instantiation); a
@@ -676,6 +644,13 @@ int32_t omf_plan_last_encoder(const omf_plan* plan) { return plan ? plan->last_e
 int omf_plan_set_fused_bracket(omf_plan* plan, int32_t on) {
   if (!plan) return fail(OMF_EINVAL, "plan is NULL");
   plan->spec_fb = on != 0 ? 1 : 0;
+  return OMF_OK;
+}
+int omf_plan_set_h16(omf_plan* plan, int32_t wide_loads, int32_t rows) {
+  if (!plan) return fail(OMF_EINVAL, "plan is NULL");
+  if (rows >= 0 && rows != 4 && rows != 8) return fail(OMF_EINVAL, "omf_plan_set_h16: rows must be 4 or 8");
+  if (wide_loads >= 0) plan->h16_wide = wide_loads != 0 ? 1 : 0;
+  if (rows >= 0) plan->h16_rows = rows;
   return OMF_OK;
 }
 int omf_plan_set_wide_levels(omf_plan* plan, int32_t on) {
@@ -927,6 +902,7 @@ static int encode_launch(omf_plan* p, EncCall c) {
       break;
     case kEncResident:
     case kEncOrdered: launch_ordered(p, c, ch.encoder); break;
+    case kEncH16: break;  // never choose_encoder's: a 16-bit arena comes in through encode_h16_impl
   }
   OMF_HIP(hipGetLastError());
   return OMF_OK;
@@ -947,7 +923,43 @@ static int encode_impl(omf_plan* p, const float* x, float alpha, int32_t s, cons
   return plan_leave(p, st);
 }
 
+// A call on a 16-bit arena: encode_launch's checks, then the two launches of omf_qsgd_h16.hip.
+static int encode_h16_impl(omf_plan* p, const void* x16, int32_t fmt, float alpha, int32_t s, const float* u,
+                           uint64_t seed, uint64_t offset, const float* norm_in, void* q, float* norm_out,
+                           bool norm_only, void* stream) {
+  if (!p) return fail(OMF_EINVAL, "plan is NULL");
+  if (fmt != 1 && fmt != 2) return fail(OMF_EINVAL, "value_format of a 16-bit arena must be 1 (bf16) or 2 (fp16)");
+  if (int r = check_bits(s)) return r;
+  const int width = (1 << s) <= 127 ? 1 : 4;
+  if (!x16 || !norm_out || (!norm_only && !q)) return fail(OMF_EINVAL, "x16, q and norm_out must be non-NULL");
+  if (!aligned(x16, 16) || (u && !aligned(u, 16)) || (q && !aligned(q, width == 1 ? 4 : 16)))
+    return fail(OMF_EINVAL, "misaligned buffer (x16, fp32 and int32 need 16 B, int8 needs 4 B alignment)");
+  if (!p->d_block) return fail(OMF_EHIP, "the plan's tables are not on the device (an earlier upload failed)");
+  DeviceGuard g(p->device);
+  if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
+  const hipStream_t st = (hipStream_t)stream;
+  if (int r = plan_enter(p, st)) return r;
+  if (!norm_only) p->last_encoder = kEncH16;
+  if (int r = h16::launch(p, EncCall{nullptr, alpha, s, u, seed, offset, norm_in, q, norm_out, norm_only, st, 0.0f,
+                                     nullptr, (uint32_t)fmt, nullptr, width},
+                          x16))
+    return r;
+  return plan_leave(p, st);
+}
+
 extern "C" {
+
+int omf_qsgd_encode_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, int32_t bit_width,
+                        const float* u, uint64_t seed, uint64_t offset, const float* norm_in, void* q_out,
+                        float* norm_out, void* stream) {
+  return encode_h16_impl(plan, x16, value_format, alpha, bit_width, u, seed, offset, norm_in, q_out, norm_out, false,
+                         stream);
+}
+
+int omf_qsgd_norms_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, float* norm_out,
+                       void* stream) {
+  return encode_h16_impl(plan, x16, value_format, alpha, 0, nullptr, 0, 0, nullptr, nullptr, norm_out, true, stream);
+}
 
 int omf_qsgd_encode(omf_plan* plan, const float* x, float alpha, int32_t bit_width, const float* u, uint64_t seed,
                     uint64_t offset, const float* norm_in, void* q_out, float* norm_out, void* stream) {

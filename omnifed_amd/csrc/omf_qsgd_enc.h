@@ -1,9 +1,10 @@
-// omf_qsgd_enc.h — device steps shared by the QSGD encoders of omf_qsgd.hip and omf_qsgd_bracket.hip
-// (gfx950).
+// omf_qsgd_enc.h — device steps shared by the QSGD encoders of omf_qsgd.hip, omf_qsgd_bracket.hip and
+// omf_qsgd_h16.hip (gfx950).
 //
 // The element math is omf_qsgd_dev.h; here is what the encoder kernels build on it: their argument
-// record, the tail-safe quad load and payload store, a thread's row loads with their scale and sum of
-// squares, the Philox draws of a row group, the quantise-and-store of a sub-chunk.  Every function is
+// record, the tail-safe quad load and payload store, a thread's row loads (fp32 arenas, and the 16-bit
+// arenas of omf_qsgd_h16.hip) with their scale and sum of squares, the Philox draws of a row group, the
+// quantise-and-store of a sub-chunk, the ticketed fold of a tensor's partials to its norm.  Every function is
 // __device__ __forceinline__ in an unnamed namespace, as the kernels are: each unit compiles its own
 // copy, and a kernel's name keeps its argument type.
 #pragma once
@@ -95,6 +96,69 @@ __device__ __forceinline__ void load_f4(const float* __restrict__ p, int64_t b, 
 template <int V, bool FULL, bool NT = false>
 __device__ __forceinline__ void load_f4(const float* __restrict__ p, int64_t b, int64_t end, float4 (&v)[V]) {
   load_f4<V, FULL, NT>(p, b, end, v, (int)threadIdx.x);
+}
+
+// ---------------------------------------------------------------- rows of a 16-bit arena
+// p holds bf16 or fp16 bit patterns; a thread's rows are the same quads as load_f4's (a quad is 8 bytes
+// here), widened to fp32 in registers, exactly: bf16 is the high half of an fp32, fp16 one v_cvt_f32_f16
+// per half of a dword.
+
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+// The two 16-bit values of dwords w0, w1 as a quad.
+template <bool BF16>
+__device__ __forceinline__ float4 cvt_h4(uint32_t w0, uint32_t w1) {
+  if (BF16)
+    return make_float4(__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xFFFF0000u), __uint_as_float(w1 << 16),
+                       __uint_as_float(w1 & 0xFFFF0000u));
+  typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+  const f16x2_t a = __builtin_bit_cast(f16x2_t, w0), b = __builtin_bit_cast(f16x2_t, w1);
+  return make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
+}
+
+// N = 2 or 4 dwords (one quad, or two adjacent ones) at element e of a range that ends at `end`: one
+// 8- or 16-byte access when whole, else the elements inside the range one by one (absent ones read 0:
+// nothing at or past `end` is touched).  p + e is aligned to the access (4 N bytes).
+template <int N, bool FULL, bool NT>
+__device__ __forceinline__ auto load_hwords(const uint16_t* p, int64_t e, int64_t end) {
+  typedef uint32_t vec_t __attribute__((ext_vector_type(N)));
+  if (FULL || e + 2 * N <= end) {
+    const vec_t* q = reinterpret_cast<const vec_t*>(p + e);
+    return NT ? __builtin_nontemporal_load(q) : *q;
+  }
+  vec_t t = 0u;
+#pragma unroll
+  for (int i = 0; i < 2 * N - 1; ++i)
+    if (e + i < end) t[i >> 1] |= (uint32_t)p[e + i] << (16 * (i & 1));
+  return t;
+}
+
+// V rows of this thread in the sub-chunk at b.  WIDE (b a multiple of 8 elements, p 16-byte aligned):
+// every global load is 16 bytes — lane 2j loads quads 2j and 2j + 1 of row k, lane 2j + 1 the same two
+// quads of row k + 1, and one DPP pair swap (quad_perm [1,0,3,2]) of the quad the other lane owns hands
+// each lane its own quad of both rows.  Else one 8-byte load per row.  Every lane of the wave is active.
+template <int V, bool FULL, bool NT, bool WIDE, bool BF16>
+__device__ __forceinline__ void load_h4(const uint16_t* __restrict__ p, int64_t b, int64_t end, float4 (&v)[V]) {
+  const int tid = (int)threadIdx.x;
+  if (!WIDE) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const u32x2_t w = load_hwords<2, FULL, NT>(p, b + 4 * ((int64_t)k * kThreads + tid), end);
+      v[k] = cvt_h4<BF16>(w[0], w[1]);
+    }
+    return;
+  }
+  static_assert(!WIDE || V % 2 == 0, "the pair swap serves two rows at a time");
+  const bool odd = (tid & 1) != 0;
+#pragma unroll
+  for (int k = 0; k + 1 < V; k += 2) {
+    const u32x4_t w = load_hwords<4, FULL, NT>(p, b + 4 * ((int64_t)(k + (odd ? 1 : 0)) * kThreads + (tid & ~1)), end);
+    // the even lane keeps w[0..1] (its quad of row k) and gives w[2..3]; the odd lane the other way round
+    const uint32_t r0 = dpp_mov<0xB1>(odd ? w[0] : w[2]), r1 = dpp_mov<0xB1>(odd ? w[1] : w[3]);
+    v[k] = cvt_h4<BF16>(odd ? r0 : w[0], odd ? r1 : w[1]);
+    v[k + 1] = cvt_h4<BF16>(odd ? w[2] : r0, odd ? w[3] : r1);
+  }
 }
 
 // The quad's four products with alpha.
@@ -200,6 +264,43 @@ __device__ __forceinline__ void quant_sub(const EncArgs& a, int64_t b, int64_t e
     load_f4<V, false, NT>(a.x, b, e, v);
     scale_f4<V>(v, a);
     quant_store<WIDTH, HAS_U, false, V>(v, a, b, e, tbegin, tensor, norm);
+  }
+}
+
+// ---------------------------------------------------------------- norm hand-off
+
+struct HandoffShared {
+  double red[kWaves];
+  uint32_t last, ok;
+  float norm;
+};
+
+// Publish one item's partial; the last arriver of the tensor folds all partials in a fixed
+// order (deterministic norm) and publishes the {tag = 1, norm} granule.  Protocol
+// (cdna_hip_programming.md §6 G16): partial stored sc1 and drained before the
+// agent-scope counter add; the last arriver reads the partials with sc1 loads.
+__device__ __forceinline__ void publish_partial(const EncArgs& a, const TensorInfo& ti, int32_t t, int32_t idx,
+                                                float acc, HandoffShared& sh) {
+  const double s = block_sum_f64((double)acc, sh.red);
+  if (threadIdx.x == 0) {
+    st_agent(&a.partials[ti.pbase + idx], (uint64_t)__double_as_longlong(s));
+    drain_vmem();
+    const uint32_t old = add_agent(&a.counters[t], 1u);
+    sh.last = (old == (uint32_t)(ti.nchunks - 1)) ? 1u : 0u;
+    // Every partial of t has arrived: reset the counter for the next launch (stream order).
+    if (sh.last) __hip_atomic_store(&a.counters[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (sh.last) {
+    double p = 0.0;
+    for (int j = threadIdx.x; j < ti.nchunks; j += kThreads)
+      p += __longlong_as_double((long long)ld_agent(&a.partials[ti.pbase + j]));
+    const double tot = block_sum_f64(p, sh.red);
+    if (threadIdx.x == 0) {
+      const float norm = finish_norm(tot, a.fmt);
+      a.norm_out[t] = norm;
+      st_agent(&a.gran[t], ((uint64_t)a.epoch << 32) | (uint64_t)__float_as_uint(norm));
+    }
   }
 }
 

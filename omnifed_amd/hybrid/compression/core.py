@@ -80,45 +80,47 @@ def compute_device(t: torch.Tensor, preferred: torch.device) -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def to_arena(t: torch.Tensor, dev: torch.device, plan: "codec.Plan") -> torch.Tensor:
-    """A 16-byte aligned fp32 arena on ``dev`` holding ``t`` flattened (no copy when already suitable)."""
+def to_arena(t: torch.Tensor, dev: torch.device, plan: "codec.Plan", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """A 16-byte aligned ``dtype`` arena on ``dev`` holding ``t`` flattened (no copy when already suitable)."""
     flat = t.detach().reshape(-1)
-    if flat.dtype == torch.float32 and flat.device == dev and flat.is_contiguous() and flat.data_ptr() % 16 == 0:
+    if flat.dtype == dtype and flat.device == dev and flat.is_contiguous() and flat.data_ptr() % 16 == 0:
         return flat
-    buf = torch.empty(max(plan.arena_end, 1), dtype=torch.float32, device=dev)
+    buf = torch.empty(max(plan.arena_end, 1), dtype=dtype, device=dev)
     buf[: flat.numel()].copy_(flat, non_blocking=False)
     return buf
 
 
-def shared_arena(flats, dev: torch.device, plan: "codec.Plan"):
-    """The arena ``flats`` already form, if they do: every flat is a contiguous fp32 view of ONE
+def shared_arena(flats, dev: torch.device, plan: "codec.Plan", dtype: torch.dtype = torch.float32):
+    """The arena ``flats`` already form, if they do: every flat is a contiguous ``dtype`` view of ONE
     storage on ``dev`` at ``base + plan.offsets[t]`` (a model's flat gradient buffer, the PS's
     average arena), 16-byte aligned and long enough for the plan — then that storage is the
     arena (no copy).  None otherwise."""
     f0 = flats[0]
-    if f0.dtype != torch.float32 or f0.device != dev:
+    if f0.dtype != dtype or f0.device != dev:
         return None
     st = f0.untyped_storage()
     sptr = st.data_ptr()
+    esz = f0.element_size()
     base = f0.storage_offset() - plan.offsets[0]
-    if base < 0 or (sptr + 4 * base) % 16 or st.nbytes() < 4 * (base + plan.arena_end):
+    if base < 0 or (sptr + esz * base) % 16 or st.nbytes() < esz * (base + plan.arena_end):
         return None
     for f, o in zip(flats, plan.offsets):
-        if (f.dtype != torch.float32 or not f.is_contiguous() or f.storage_offset() != base + o
+        if (f.dtype != dtype or not f.is_contiguous() or f.storage_offset() != base + o
                 or f.untyped_storage().data_ptr() != sptr):
             return None
-    return torch.empty(0, dtype=torch.float32, device=dev).set_(st, base, (plan.arena_end,))
+    return torch.empty(0, dtype=dtype, device=dev).set_(st, base, (plan.arena_end,))
 
 
-def gather_arena(flats, dev: torch.device, plan: "codec.Plan") -> torch.Tensor:
-    """The fp32 update arena of ``flats`` (flat tensors in plan order): the storage they already
-    share (``shared_arena``), else a fresh arena they are copied into (bf16/fp16 -> fp32 exact)."""
+def gather_arena(flats, dev: torch.device, plan: "codec.Plan", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The update arena of ``flats`` (flat tensors in plan order) in ``dtype``: the storage they already
+    share (``shared_arena``), else a fresh arena they are copied into.  fp32 by default (bf16/fp16 ->
+    fp32 is exact); bf16 / fp16 flats gathered in their own dtype are copied bit for bit, no upcast."""
     if len(flats) == 1:
-        return to_arena(flats[0], dev, plan)
-    x = shared_arena(flats, dev, plan)
+        return to_arena(flats[0], dev, plan, dtype)
+    x = shared_arena(flats, dev, plan, dtype)
     if x is not None:
         return x
-    x = torch.empty(plan.arena_end, dtype=torch.float32, device=dev)
+    x = torch.empty(plan.arena_end, dtype=dtype, device=dev)
     for f, o, n in zip(flats, plan.offsets, plan.sizes):
         x[o:o + n].copy_(f.detach().reshape(-1))
     return x
