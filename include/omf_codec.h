@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 118
+#define OMF_ABI_VERSION 119
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -132,7 +132,7 @@ int omf_plan_set_encode_strategy(omf_plan* plan, int32_t strategy);
 int32_t omf_plan_encode_strategy(const omf_plan* plan);
 /* The encoder the plan's latest encode (or fused PS step) launched: 0 register-resident +
  * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in),
- * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -288,6 +288,42 @@ int omf_div_f32(float* y, int64_t n, float divisor, void* stream);
  */
 int omf_qsgd_decode_sum(omf_plan* plan, const void* const* q, const float* const* norm, int32_t nclients,
                         int32_t width, int32_t levels, float* y_out, int32_t init, float divisor, void* stream);
+
+/*
+ * Opt-in QSGD with bucket norms (NOT reference-compatible: the reference scales a tensor by one norm).
+ * Consecutive groups of bucket_size = d elements of a tensor — d a power of two in [64, 4096], buckets
+ * restart at every tensor, the last may be short — are quantised each against its own norm, by the rules
+ * of omf_qsgd_encode applied to the bucket: xs = fl32(x * alpha), norm_b = fp32 L2 norm of xs over the
+ * bucket, levels against norm_b (all zero for a zero norm_b), decode fl32(fl32(norm_b * q) / fl32(levels)).
+ * Tensor t has ceil(sizes[t] / d) norms; a bucket-norm arena holds them tensor after tensor, bucket after
+ * bucket (omf_qsgd_bucket_count entries, fp32).  The draws (u, or Philox from seed / offset) and the payload
+ * arena are omf_qsgd_encode's.  fp32 arenas only.  A bucket's norm bits depend only on its values and d
+ * (fixed summation order: omnifed_amd/csrc/omf_qsgd_bucket.h).  One launch per call, x read once, no
+ * in-kernel wait (omf_plan_check has nothing to report for it); the first call at a bucket size on a plan
+ * uploads one small table (synchronous), later calls neither allocate nor synchronise.
+ *   omf_qsgd_bucket_count         entries of the plan's bucket-norm arena; -1 for a bad bucket_size.
+ *   omf_qsgd_encode_bucketed      bnorm_in (NULL or a bucket-norm arena): used in place of the computed
+ *                                 norms and copied to bnorm_out, as omf_qsgd_encode's norm_in.
+ *   omf_qsgd_norms_bucketed       the norms alone: the same bits as the encode's.
+ *   omf_qsgd_decode_bucketed      omf_qsgd_decode with a norm per bucket; only the tensors' elements of
+ *                                 y_out are written.
+ *   omf_qsgd_decode_sum_bucketed  omf_qsgd_decode_sum with a norm per bucket (bnorm: nclients device
+ *                                 pointers): the same order, padding fill, division, chaining in groups of
+ *                                 8 clients and errors.
+ * OMF_EINVAL: a bad bucket_size, and whatever the per-tensor calls refuse (NULL or misaligned buffers, a bad
+ * width, levels or bit_width, y_out overlapping a payload or norm buffer).
+ */
+int64_t omf_qsgd_bucket_count(const omf_plan* plan, int64_t bucket_size);
+int omf_qsgd_encode_bucketed(omf_plan* plan, const float* x, float alpha, int32_t bit_width, int64_t bucket_size,
+                             const float* u, uint64_t seed, uint64_t offset, const float* bnorm_in, void* q_out,
+                             float* bnorm_out, void* stream);
+int omf_qsgd_norms_bucketed(omf_plan* plan, const float* x, float alpha, int64_t bucket_size, float* bnorm_out,
+                            void* stream);
+int omf_qsgd_decode_bucketed(omf_plan* plan, const void* q, int32_t width, int32_t levels, int64_t bucket_size,
+                             const float* bnorm, float* y_out, int32_t accumulate, void* stream);
+int omf_qsgd_decode_sum_bucketed(omf_plan* plan, const void* const* q, const float* const* bnorm, int32_t nclients,
+                                 int32_t width, int32_t levels, int64_t bucket_size, float* y_out, int32_t init,
+                                 float divisor, void* stream);
 
 /*
  * Opt-in bit-packed QSGD wire (NOT reference-compatible, a new

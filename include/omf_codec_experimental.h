@@ -63,6 +63,11 @@ int omf_plan_set_fused_bracket(omf_plan* plan, int32_t on);
  * or 8 rows of 1024 elements per quantise workgroup.  A negative argument keeps the setting.  Identical
  * norms and payloads either way. */
 int omf_plan_set_h16(omf_plan* plan, int32_t wide_loads, int32_t rows);
+/* The bucketed encoder's rows of 1024 elements per workgroup (omf_qsgd_encode_bucketed;
+ * scripts/bucketed_encode_ab.py times them): 4 (the default: measured fastest), 8 or 16; static_d != 0 (the
+ * default: measured no slower at any bucket size, faster from 1024 up): the 4-row kernels with the bucket size
+ * at compile time, else as a kernel argument (8 and 16 rows always).  Identical norms and payloads. */
+int omf_plan_set_bucket_rows(omf_plan* plan, int32_t rows, int32_t static_d);
 /* Diagnostics of the last bracketed single-read encode (strategy 3; synchronises `stream`,
  * not for the hot path): out[0] tensors requantised whole (norm outside the sampled bracket,
  * a wave's undecided-quad slot overflowed, or a degenerate sample), out[1] of those the

@@ -32,6 +32,22 @@ def arena_layout(sizes: Sequence[int], align: int = ALIGN_ELEMS) -> Tuple[List[i
     return offs, max(cur, align)
 
 
+BUCKET_SIZES = tuple(1 << l for l in range(6, 13))  # bucketed QSGD: 64 .. 4096 (csrc/omf_qsgd_bucket.h)
+
+
+def bucket_layout(sizes: Sequence[int], bucket_size: int) -> Tuple[List[int], int]:
+    """Bucketed QSGD's norm arena for tensors of ``sizes`` (csrc/omf_qsgd_bucket.h): tensor t has
+    ``ceil(sizes[t] / bucket_size)`` norms starting at ``boff[t]``; returns ``(boff, nb)``."""
+    d = int(bucket_size)
+    if d not in BUCKET_SIZES:
+        raise ValueError(f"bucket_size={bucket_size!r}: expected a power of two in [64, 4096]")
+    boff, nb = [], 0
+    for n in sizes:
+        boff.append(nb)
+        nb += -(-int(n) // d)
+    return boff, nb
+
+
 def storage_width(levels: int) -> int:
     """qsgd.py:18-21: payload bits per element (8 while levels <= 127, else 32)."""
     return 8 if levels <= 127 else 32
@@ -164,6 +180,7 @@ class Plan:
         self._counts_cache: Dict[tuple, tuple] = {}
         self._packed_cache: Dict[tuple, tuple] = {}
         self._topk_cache: Dict[float, tuple] = {}
+        self._bucket_cache: Dict[int, tuple] = {}
         self.topk_reordered = 0  # tensors the latest tie_order="torch" encode rewrote (diagnostics)
         # the library's choice (by arena size, or OMF_ENCODE_STRATEGY)
         self.strategy = STRATEGIES[int(L.omf_plan_encode_strategy(h))]
@@ -267,9 +284,10 @@ class Plan:
     @property
     def last_encoder(self) -> str:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
-        "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena) or "none"."""
+        "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms) or
+        "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
-        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {5: "norm_in", 6: "h16"}.get(code, "none")
+        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {5: "norm_in", 6: "h16", 7: "bucketed"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -540,6 +558,139 @@ class Plan:
         check(lib().omf_qsgd_decode_sum(self._h, qp, npp, n, width, levels, _ptr(y_out), 1 if init else 0, d,
                                         ctypes.c_void_p(st)), "omf_qsgd_decode_sum")
         return y_out
+
+    # ------------------------------------------------------------ bucket norms (opt-in)
+    def bucket_layout(self, bucket_size: int) -> Tuple[List[int], int]:
+        """``bucket_layout(self.sizes, bucket_size)``: the tensors' offsets into the plan's bucket-norm arena
+        and its length (omf_qsgd_bucket_count)."""
+        got = self._bucket_cache.get(int(bucket_size))
+        if got is None:
+            got = self._bucket_cache[int(bucket_size)] = bucket_layout(self.sizes, bucket_size)
+        return got
+
+    def _bucket_norms(self, t: Optional[torch.Tensor], name: str, nb: int) -> torch.Tensor:
+        if t is None:
+            return torch.empty(nb, dtype=torch.float32, device=self.device)
+        _need(t, name, torch.float32, self.device, nb, 4)
+        return t
+
+    def qsgd_encode_bucketed(self, x: torch.Tensor, bit_width: int, bucket_size: int,
+                             q_out: Optional[torch.Tensor] = None, bnorm_out: Optional[torch.Tensor] = None,
+                             alpha: float = 1.0, u: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+                             bnorm_in: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        """omf_qsgd_encode_bucketed: ``qsgd_encode`` with one norm per bucket of ``bucket_size`` consecutive
+        elements of a tensor; returns ``(q, bnorms)``, ``bnorms`` the plan's bucket-norm arena
+        (``bucket_layout``).  fp32 arenas only: a bf16 / fp16 ``x`` raises ``ValueError``."""
+        if getattr(x, "dtype", None) in H16_FORMATS:
+            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        _, nb = self.bucket_layout(bucket_size)
+        s = int(bit_width)
+        if not 0 <= s <= 30:
+            raise ValueError("bit_width must be in [0, 30]")
+        width = storage_width(2 ** s)
+        qdt = torch.int8 if width == 8 else torch.int32
+        dev = self.device
+        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        if q_out is None:
+            q_out = torch.empty(self.payload_elems(width), dtype=qdt, device=dev)
+        _need(q_out, "q_out", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        if u is not None:
+            _need(u, "u", torch.float32, dev, self.arena_end, 16)
+        if bnorm_in is not None:
+            _need(bnorm_in, "bnorm_in", torch.float32, dev, nb, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_encode_bucketed(self._h, _ptr(x), float(alpha), s, int(bucket_size), _ptr(u),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                                 _ptr(bnorm_in), _ptr(q_out), _ptr(bnorm_out), ctypes.c_void_p(st)),
+                  "omf_qsgd_encode_bucketed")
+        return q_out, bnorm_out
+
+    def qsgd_norms_bucketed(self, x: torch.Tensor, bucket_size: int, alpha: float = 1.0,
+                            bnorm_out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
+        """The bucket norms alone (omf_qsgd_norms_bucketed): the bits ``qsgd_encode_bucketed`` writes."""
+        if getattr(x, "dtype", None) in H16_FORMATS:
+            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        _, nb = self.bucket_layout(bucket_size)
+        _need(x, "x", torch.float32, self.device, self.arena_end, 16)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        st = stream if stream is not None else _stream(self.device)
+        with self._lock:
+            check(lib().omf_qsgd_norms_bucketed(self._h, _ptr(x), float(alpha), int(bucket_size), _ptr(bnorm_out),
+                                                ctypes.c_void_p(st)), "omf_qsgd_norms_bucketed")
+        return bnorm_out
+
+    def qsgd_decode_bucketed(self, q: torch.Tensor, width: int, levels: int, bucket_size: int, bnorm: torch.Tensor,
+                             y_out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                             stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_bucketed: ``qsgd_decode`` with one norm per bucket."""
+        width, levels = int(width), int(levels)
+        if width not in (8, 32):
+            raise ValueError(f"unsupported width={width}")
+        if levels <= 0:
+            raise ValueError(f"invalid level={levels}")
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        _need(q, "q", torch.int8 if width == 8 else torch.int32, dev, self.arena_end, 4 if width == 8 else 16)
+        _need(bnorm, "bnorm", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:  # the first call at a bucket size makes the plan's table
+            check(lib().omf_qsgd_decode_bucketed(self._h, _ptr(q), width, levels, int(bucket_size), _ptr(bnorm),
+                                                 _ptr(y_out), 1 if accumulate else 0, ctypes.c_void_p(st)),
+                  "omf_qsgd_decode_bucketed")
+        return y_out
+
+    def qsgd_decode_sum_bucketed(self, qs: Sequence[torch.Tensor], width: int, levels: int, bucket_size: int,
+                                 bnorms: Sequence[torch.Tensor], y_out: Optional[torch.Tensor] = None,
+                                 init: bool = False, divisor: Optional[float] = None,
+                                 stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_sum_bucketed: ``qsgd_decode_sum`` over clients' bucketed payloads, ``bnorms[k]``
+        client k's bucket-norm arena."""
+        width, levels = int(width), int(levels)
+        if width not in (8, 32):
+            raise ValueError(f"unsupported width={width}")
+        if levels <= 0:
+            raise ValueError(f"invalid level={levels}")
+        qs, bnorms = list(qs), list(bnorms)
+        if not qs or len(qs) != len(bnorms):
+            raise ValueError(f"qsgd_decode_sum_bucketed needs one norm arena per payload and at least one "
+                             f"({len(qs)}, {len(bnorms)})")
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        qdt = torch.int8 if width == 8 else torch.int32
+        for k, (q, nm) in enumerate(zip(qs, bnorms)):
+            _need(q, f"qs[{k}]", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+            _need(nm, f"bnorms[{k}]", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if init:
+                raise ValueError("init=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        n = len(qs)
+        qp = (ctypes.c_void_p * n)(*[q.data_ptr() for q in qs])
+        npp = (ctypes.c_void_p * n)(*[nm.data_ptr() for nm in bnorms])
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_decode_sum_bucketed(self._h, qp, npp, n, width, levels, int(bucket_size), _ptr(y_out),
+                                                     1 if init else 0, d, ctypes.c_void_p(st)),
+                  "omf_qsgd_decode_sum_bucketed")
+        return y_out
+
+    def set_bucket_rows(self, rows: int = 4, static_d: bool = True) -> None:
+        """Experiment hook of the bucketed encoder (omf_plan_set_bucket_rows): the defaults, or 8 / 16 rows (and, at 4 rows, the
+        bucket size as a kernel argument instead of at compile time); rows of
+        1024 elements per workgroup.  Identical results."""
+        with self._lock:
+            check(lib().omf_plan_set_bucket_rows(self._h, int(rows), 1 if static_d else 0), "omf_plan_set_bucket_rows")
 
     # ------------------------------------------------------------ bit-packed wire (opt-in)
     def packed_words(self, levels: int) -> int:

@@ -53,6 +53,16 @@ struct omf_plan {
   // served where every tensor starts on a 16-byte boundary of such an arena
   int32_t h16_wide = 0, h16_rows = 4;
   bool h16_aligned = false;
+  // bucketed QSGD (omf_qsgd_bucketed.hip): per allowed bucket size 2^(6 + i), the tensors' offsets into the
+  // bucket-norm arena (device; made at the first call at that size, owned through d_lazy) and the arena's
+  // length; the encoder's rows per workgroup (omf_plan_set_bucket_rows): 4 measured fastest at every bucket
+  // size (profiles/bucketed_encode_ab.json: Llama-400M d = 512 0.410 ms against 0.437 with 8 and 0.521 with 16),
+  // and d at compile time no slower than as a kernel argument at any size, faster from d = 1024 up (Llama-400M
+  // d = 4096 0.377 ms against 0.409) and at every size on ResNet-18
+  int64_t* d_boff[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int64_t bucket_nb[7] = {0, 0, 0, 0, 0, 0, 0};
+  int32_t bucket_rows = 4;
+  bool bucket_static_d = true;   // the 4-row kernel with d at compile time (omf_plan_set_bucket_rows)
   // ---- the plan's block: one device allocation, carved by upload_plan (omf_qsgd.hip) in this order
   void* d_block = nullptr;
   uint8_t* d_sync = nullptr;    // [ticket u32, err u32, pad 8][counters u32 x nt, pad16][granules u64 x nt, pad16]

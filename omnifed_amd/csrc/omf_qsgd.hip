@@ -903,6 +903,7 @@ static int encode_launch(omf_plan* p, EncCall c) {
     case kEncResident:
     case kEncOrdered: launch_ordered(p, c, ch.encoder); break;
     case kEncH16: break;  // never choose_encoder's: a 16-bit arena comes in through encode_h16_impl
+    case kEncBucketed: break;  // nor this: omf_qsgd_encode_bucketed (omf_qsgd_bucketed.hip)
   }
   OMF_HIP(hipGetLastError());
   return OMF_OK;

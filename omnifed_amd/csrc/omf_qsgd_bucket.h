@@ -1,0 +1,133 @@
+// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip), one copy of each.  Not part of the
+// C ABI.  The host rules come first and are plain C++ with no HIP header; the device rules follow under
+// __HIPCC__.
+//
+// Bucketed QSGD quantises consecutive groups of d elements of a tensor, each against its own L2 norm
+// (Alistarh et al., QSGD, §3.3: the variance bound min(n / L^2, sqrt(n) / L) holds per bucket, with n = d).
+//   d            a power of two in {64, 128, ..., 4096};
+//   bucket j     of tensor t is elements [j d, min((j + 1) d, n_t)) of the tensor's flat order: buckets
+//                restart at every tensor, the last one may be short;
+//   nb_t         ceil(n_t / d) buckets;
+//   boff[t]      sum of nb_u over u < t: where tensor t's norms start in a plan's bucket-norm arena, which
+//                holds nb = sum of nb_t fp32 norms.
+// Per bucket the semantics are the per-tensor ones on the bucket's elements: v = fl32(alpha x),
+// norm_b = fl32(sqrt(sum v^2)) in fp32, levels from qsgd_quad with Divisor(norm_b), zero levels for a zero
+// norm, decode fl32(fl32(norm_b q) / L).
+//
+// The summation order of a bucket's sum of squares (fp32 throughout, no contraction other than the fma chain
+// written here) is fixed, so a bucket's norm bits depend only on its values and on d — not on the arena
+// offset, the plan, the workgroup's size or the run.  With the bucket's elements numbered from its begin and
+// absent elements of a short last bucket taken as +0 (adding +0 to a sum of squares changes no bit):
+//   1. quad sums      s_i = fma(v3, v3, fma(v2, v2, fma(v1, v1, fma(v0, v0, +0)))) over elements 4i .. 4i + 3;
+//   2. rows           d > 1024 only: quad i of the bucket's row r is i = 256 r + lane; the rows' sums of one
+//                     lane are added pairwise, r ^ 1 and then (d = 4096) r ^ 2;
+//   3. lanes          a butterfly over the quads (or lane sums) of a row: s += s[lane ^ o] for o = 1, 2, 4, 8,
+//                     then 16 (d >= 128) and 32 (d >= 256): after it every lane of the bucket's aligned group
+//                     of min(d / 4, 64) lanes holds the same bits (fp32 + commutes exactly);
+//   4. waves          d >= 512: the groups of 64 lanes are added as w ^ 1 (d = 512: (g0 + g1)), then w ^ 2
+//                     (d >= 1024: ((g0 + g1) + (g2 + g3)));
+//   5. norm_b = sqrtf(sum), correctly rounded.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace omf {
+namespace bucket {
+
+// ---------------------------------------------------------------- host rules
+
+constexpr int kMinLog2 = 6, kMaxLog2 = 12;         // d = 64 .. 4096
+constexpr int kSizes = kMaxLog2 - kMinLog2 + 1;    // the allowed sizes (a plan caches one table each)
+
+// log2 d of an allowed bucket size, else -1.
+inline int log2_size(int64_t d) {
+  for (int l = kMinLog2; l <= kMaxLog2; ++l)
+    if (d == ((int64_t)1 << l)) return l;
+  return -1;
+}
+
+// nb_t of a tensor of n > 0 elements.
+inline int64_t count(int64_t n, int logd) { return (n + (((int64_t)1 << logd) - 1)) >> logd; }
+
+// boff[0 .. nt) of the tensors' sizes; returns nb.
+inline int64_t offsets(const int64_t* sizes, int32_t nt, int logd, int64_t* boff) {
+  int64_t nb = 0;
+  for (int32_t t = 0; t < nt; ++t) {
+    if (boff) boff[t] = nb;
+    nb += count(sizes[t], logd);
+  }
+  return nb;
+}
+
+}  // namespace bucket
+}  // namespace omf
+
+#ifdef __HIPCC__
+#include "omf_common.h"
+
+namespace omf {
+namespace bucket {
+
+// ---------------------------------------------------------------- device rules
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) { return __uint_as_float(dpp_mov<CTRL>(__float_as_uint(v))); }
+
+// Step 3: the butterfly over the aligned group of min(2^(logd - 2), 64) lanes this lane belongs to; every
+// lane of the group ends with the group's sum.  logd is wave-uniform (a kernel argument), and every lane of
+// the wave must be active.  No LDS traffic: DPP inside a row of 16 lanes, v_permlane16_swap /
+// v_permlane32_swap of s with itself across rows (the two results are {own | partner}, as wave_sum_f64).
+__device__ __forceinline__ float lane_group_sum(float s, int logd) {
+  s = __fadd_rn(s, dpp_f32<0xB1>(s));                   // lane ^ 1: quad_perm [1,0,3,2]
+  s = __fadd_rn(s, dpp_f32<0x4E>(s));                   // lane ^ 2: quad_perm [2,3,0,1]
+  s = __fadd_rn(s, dpp_f32<0x1B>(dpp_f32<0x141>(s)));   // lane ^ 4: row_half_mirror, then quad_perm [3,2,1,0]
+  s = __fadd_rn(s, dpp_f32<0x128>(s));                  // lane ^ 8: row_ror:8
+  if (logd >= 7) {
+    const uint32_t b = __float_as_uint(s);
+    const auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
+    s = __fadd_rn(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  }
+  if (logd >= 8) {
+    const uint32_t b = __float_as_uint(s);
+    const auto r = __builtin_amdgcn_permlane32_swap(b, b, false, false);
+    s = __fadd_rn(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  }
+  return s;
+}
+
+// Steps 2-4 over a thread's V rows of per-quad sums (step 1's): s[k] becomes the sum of squares of the bucket
+// that holds this thread's quad of row k.  Rows are counted from a multiple of 4 rows of the tensor, so the
+// rows of one bucket (d > 1024) are k ^ 1 and k ^ 2 in the thread's own registers.  xch: V x kWaves floats of
+// LDS, one exchange (one barrier) for every row, only from d = 512 up; called by the whole workgroup.
+template <int V>
+__device__ __forceinline__ void bucket_sums(float (&s)[V], int logd, float (*xch)[kWaves]) {
+  static_assert(V % 4 == 0, "whole buckets of 4096 elements");
+  if (logd >= 11) {
+#pragma unroll
+    for (int k = 0; k < V; k += 2) s[k] = s[k + 1] = __fadd_rn(s[k], s[k + 1]);
+  }
+  if (logd >= 12) {
+#pragma unroll
+    for (int k = 0; k < V; k += 4) s[k] = s[k + 1] = s[k + 2] = s[k + 3] = __fadd_rn(s[k], s[k + 2]);
+  }
+#pragma unroll
+  for (int k = 0; k < V; ++k) s[k] = lane_group_sum(s[k], logd);
+  if (logd < 9) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) xch[k][wave] = s[k];
+  }
+  __syncthreads();
+  const int w0 = wave & 2;
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    if (logd == 9) s[k] = __fadd_rn(xch[k][w0], xch[k][w0 + 1]);
+    else s[k] = __fadd_rn(__fadd_rn(xch[k][0], xch[k][1]), __fadd_rn(xch[k][2], xch[k][3]));
+  }
+}
+
+}  // namespace bucket
+}  // namespace omf
+#endif  // __HIPCC__

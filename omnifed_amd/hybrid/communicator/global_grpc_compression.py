@@ -35,6 +35,7 @@ import torch
 
 from . import global_grpc_pb2
 from ..compression.qsgd import (
+    QSGD_BUCKETED_COMPRESSION_NAME,
     QSGD_COMPRESSION_NAME,
     QSGD_PACKED_COMPRESSION_NAME,
     QSGDQuantCompression,
@@ -50,7 +51,7 @@ GlobalHybridCompressor = Union[TopKCompression, QSGDQuantCompression]
 
 _QSGD_NUMPY_DTYPES = {8: np.int8, 32: np.int32}
 _QSGD_TORCH_DTYPES = {8: torch.int8, 32: torch.int32}
-_QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME)
+_QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME)
 _TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
 # the two types that share the packed index wire: a message or an update may mix them
 _TOPK_PACKED_TYPES = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
@@ -91,23 +92,29 @@ def compression_mode_name(compressor: Optional[GlobalHybridCompressor]) -> str:
 
 def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_ratio: float = 0.01,
                             bit_width: int = 8, device="cpu", packed_wire: bool = False,
-                            value_bits=None) -> Optional[GlobalHybridCompressor]:
+                            value_bits=None, bucket_size=None) -> Optional[GlobalHybridCompressor]:
     """global_grpc_compression.py:35-52.  ``packed_wire`` (default off): the scheme's opt-in bit-packed
     wire — ``QSGDBitPackedCompression`` (the levels in ceil(log2(2L + 1)) bits) or
     ``TopKBitPackedCompression`` (the indices in max(1, bit_length(n - 1)) bits); neither is readable
     by the reference.  ``value_bits`` (default None; needs ``scheme="topk"`` and ``packed_wire=True``):
     ``TopKQuantPackedCompression`` layers, the selected values as QSGD levels of 2^value_bits against
-    max |v| in value_bits + 2 bits each, the quantisation error fed back through the residual."""
+    max |v| in value_bits + 2 bits each, the quantisation error fed back through the residual.
+    ``bucket_size`` (default None; needs ``scheme="qsgd"`` and no ``packed_wire``): ``QSGDBucketedCompression``
+    layers, every bucket of that many consecutive elements (a power of two in [64, 4096]) quantised against
+    its own norm; fp32 tensors only."""
     if not enabled:
         return None
     scheme_norm = str(scheme).lower()
+    if bucket_size is not None and scheme_norm != "qsgd":
+        raise ValueError(f"bucket_size requires scheme='qsgd' (got scheme={scheme!r})")
     if value_bits is not None and scheme_norm != "topk":
         raise ValueError(f"value_bits requires scheme='topk' (got scheme={scheme!r})")
     if scheme_norm == "topk":
         return TopKCompression(device=device, compress_ratio=float(compress_ratio), packed_wire=bool(packed_wire),
                                value_bits=value_bits)
     if scheme_norm == "qsgd":
-        return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire))
+        return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire),
+                                    bucket_size=bucket_size)
     raise ValueError(f"Unsupported global_compression.scheme={scheme!r}; expected 'topk' or 'qsgd'")
 
 
@@ -143,8 +150,9 @@ def hybrid_global_compressor_from_cfg(cfg, device="cpu") -> Optional[GlobalHybri
     bit_width = int(_select(cfg, "engine.hybrid.global_compression.bit_width", 8))
     packed = bool(_select(cfg, "engine.hybrid.global_compression.packed_wire", False))  # opt-in, ours
     value_bits = _select(cfg, "engine.hybrid.global_compression.value_bits", None)  # opt-in, ours
+    bucket_size = _select(cfg, "engine.hybrid.global_compression.bucket_size", None)  # opt-in, ours
     return build_global_compressor(enabled=enabled, scheme=scheme, compress_ratio=ratio, bit_width=bit_width,
-                                   device=device, packed_wire=packed, value_bits=value_bits)
+                                   device=device, packed_wire=packed, value_bits=value_bits, bucket_size=bucket_size)
 
 
 # ---------------------------------------------------------------- layer builders (host)
@@ -185,6 +193,17 @@ def qsgd_packed_layer_from_payload(name: str, shape, packed: bytes, norm: float,
     layer.meta_tensor_dtype = "torch.float32"
     layer.width = bits
     layer.level = int(levels)
+    return layer
+
+
+def qsgd_bucketed_layer_from_payload(name: str, shape, payload: bytes, bnorms, width: int, levels: int,
+                                     bucket_size: int):
+    """The opt-in bucketed QSGD ``LayerState``: the QSGD layer's values, width and level; ``meta_tensor`` = the
+    tensor's ceil(n / d) fp32 bucket norms (little-endian), and d in ``param_shape``."""
+    layer = qsgd_layer_from_payload(name, shape, payload, 0.0, width, levels)
+    layer.compression_type = QSGD_BUCKETED_COMPRESSION_NAME
+    layer.meta_tensor = np.ascontiguousarray(bnorms, dtype="<f4").tobytes()
+    layer.param_shape.append(int(bucket_size))
     return layer
 
 
@@ -289,7 +308,8 @@ def _encode_qsgd_layer(name: str, tensor: torch.Tensor, compressor: QSGDQuantCom
     """global_grpc_compression.py:101-123, payload produced on the GPU."""
     if not should_compress_tensor(tensor):
         return _encode_dense_layer(name, _weighted(tensor, weight))
-    if getattr(compressor, "packed_wire", False) or tensor.dtype != torch.float32:
+    if (getattr(compressor, "packed_wire", False) or getattr(compressor, "bucket_size", None) is not None
+            or tensor.dtype != torch.float32):
         return encode_updates_dict({name: tensor}, compressor, weight=weight)[0]
     (q, norm, width, levels), = compressor.encode_flat([tensor.detach().reshape(-1)], alpha=_alpha(weight))
     if width == -1:
@@ -473,6 +493,21 @@ def _check_packed_fields(layer):
         _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported width={layer.width}")
 
 
+def _check_bucketed_fields(layer):
+    """The bucketed layer's fields: the bucket size, one norm per bucket, the plain layer's width and level."""
+    d = int(layer.param_shape[0]) if len(layer.param_shape) == 1 else 0
+    if d not in codec.BUCKET_SIZES:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported bucket size {list(layer.param_shape)}")
+    nb = -(-_layer_numel(layer) // d)
+    if not layer.meta_tensor or len(layer.meta_tensor) != 4 * nb:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r}: meta_tensor of {len(layer.meta_tensor)} bytes, "
+                            f"expected {4 * nb} ({nb} bucket norms)")
+    if layer.width not in _QSGD_NUMPY_DTYPES:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported width={layer.width}")
+    if layer.level <= 0:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r} has invalid level={layer.level}")
+
+
 def _check_qsgd_layer(layer, payload: bytes):
     _check_qsgd_fields(layer)
     _check_qsgd_payload(layer, payload)
@@ -485,8 +520,12 @@ def _check_packed_layer(layer, payload: bytes):
 
 def _decode_qsgd_layer(layer, *, device=None) -> torch.Tensor:
     """global_grpc_compression.py:163-182, decoded on the GPU."""
-    if layer.compression_type == QSGD_PACKED_COMPRESSION_NAME:
-        _check_packed_layer(layer, layer.values_data)
+    if layer.compression_type in (QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME):
+        if layer.compression_type == QSGD_PACKED_COMPRESSION_NAME:
+            _check_packed_layer(layer, layer.values_data)
+        else:
+            _check_bucketed_fields(layer)
+            _check_qsgd_payload(layer, layer.values_data)
         shape = tuple(layer.original_shape)
         out_dev = _out_device(None, device)
         if int(np.prod(shape)) == 0:
@@ -543,6 +582,8 @@ def wire_size(layers) -> Dict[str, int]:
             payload += len(L.values_data) + len(L.indices_data) + 4 * len(L.param_update)
             if L.compression_type == TOPK_QUANT_COMPRESSION_NAME:
                 payload += len(L.meta_tensor)  # the scale
+        if L.compression_type == QSGD_BUCKETED_COMPRESSION_NAME:
+            payload += len(L.meta_tensor)  # the bucket norms
         shape = tuple(L.original_shape) or tuple(L.param_shape)
         dense += 4 * int(np.prod(shape)) if shape else 0
     return {"wire_bytes": wire, "payload_bytes": payload, "dense_fp32_bytes": dense, "layers": len(layers)}
@@ -703,6 +744,30 @@ def qsgd_layers_from_arena(plan, q: torch.Tensor, norms: torch.Tensor, names, sh
     return layers
 
 
+def qsgd_bucketed_layers_from_arena(plan, q: torch.Tensor, bnorms: torch.Tensor, names, shapes, levels: int,
+                                    bucket_size: int, stream=None) -> list:
+    """``qsgd_layers_from_arena`` for a bucketed encode: the bucket-norm arena copied first, then the payload
+    arena in chunks.  A tensor whose bucket norms are all zero gets ``None`` (the dense passthrough)."""
+    stream = torch.cuda.current_stream(plan.device) if stream is None else stream
+    width, _ = choose_qsgd_storage_width(levels)
+    boff, nb = plan.bucket_layout(bucket_size)
+    with _STAGING.lease("encode_norms", 4 * nb) as h:
+        nh = h.buf.view(torch.float32)
+        with torch.cuda.stream(stream):
+            nh[:nb].copy_(bnorms[:nb], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        ev.synchronize()
+        host = nh[:nb].numpy().copy()
+    mine = [host[b0:b1] for b0, b1 in zip(boff, boff[1:] + [nb])]
+    isz = q.element_size()
+    spans = [(o * isz, n * isz if m.any() else 0) for o, n, m in zip(plan.offsets, plan.sizes, mine)]
+    layers: List = [None] * plan.nt
+    for k, payload in hostio.device_to_bytes(q, spans, stream=stream):
+        layers[k] = qsgd_bucketed_layer_from_payload(names[k], shapes[k], payload, mine[k], width, levels, bucket_size)
+    return layers
+
+
 def _encode_updates(updates, compressor, weight) -> list:
     if isinstance(compressor, TopKCompression) and _topk_batchable(list(updates.values())):
         return _encode_topk_updates(updates, compressor, weight)
@@ -716,11 +781,21 @@ def _encode_updates(updates, compressor, weight) -> list:
             raise ValueError(f"QSGD bit_width={compressor.s} out of range [0, 30]")
         flats = [updates[names[i]].detach().reshape(-1) for i in comp_idx]
         dev = compute_device(flats[0], compressor.device)
-        from ..compression.qsgd import encode_groups
+        from ..compression.qsgd import encode_bucketed, encode_groups
 
-        groups = encode_groups(flats, compressor.s, dev, compressor.rng, compressor._next_call(),
-                               alpha=_alpha(weight), key=compressor.philox_key())
         levels = 2**compressor.s
+        if compressor.bucket_size is not None:  # one launch, one norm per bucket
+            plan, q, bn = encode_bucketed(flats, compressor.s, compressor.bucket_size, dev, compressor._next_call(),
+                                          alpha=_alpha(weight), key=compressor.philox_key())
+            got = qsgd_bucketed_layers_from_arena(plan, q, bn, [names[i] for i in comp_idx],
+                                                  [tuple(updates[names[i]].shape) for i in comp_idx], levels,
+                                                  compressor.bucket_size)
+            groups = []
+            for i, L in zip(comp_idx, got):
+                layers[i] = L
+        else:
+            groups = encode_groups(flats, compressor.s, dev, compressor.rng, compressor._next_call(),
+                                   alpha=_alpha(weight), key=compressor.philox_key())
         for plan, q, norms, members in groups:  # one group per dtype (normally one)
             idx = [comp_idx[m] for m in members]
             got = qsgd_layers_from_arena(plan, q, norms, [names[i] for i in idx],
@@ -742,11 +817,19 @@ def _decode_qsgd_batch(layers, dev: torch.device, host: bool = False):
     and the plan (layer i at ``[plan.offsets[i], + plan.sizes[i])``).  ``host``: the arena is
     returned on the CPU (``_decode_qsgd_to_host``).
     """
-    if host and layers[0].compression_type != QSGD_PACKED_COMPRESSION_NAME:
+    if host and layers[0].compression_type == QSGD_COMPRESSION_NAME:
         return _decode_qsgd_to_host(layers, dev)
     width, level = layers[0].width, layers[0].level
     sizes = [max(int(np.prod(tuple(L.original_shape))), 1) for L in layers]
     plan = codec.Plan.get(sizes, device=dev)
+    if layers[0].compression_type == QSGD_BUCKETED_COMPRESSION_NAME:  # the layers share d (_scan_layers)
+        d = int(layers[0].param_shape[0])
+        bn = np.concatenate([np.frombuffer(L.meta_tensor, dtype="<f4") for L in layers]).astype(np.float32)
+        isz = width // 8
+        qd = torch.empty(plan.payload_elems(width), dtype=_QSGD_TORCH_DTYPES[width], device=dev)
+        items = [(o * isz, (lambda L=L: L.values_data)) for L, o in zip(layers, plan.offsets)]
+        hostio.bytes_to_device(items, qd, isz * plan.arena_end, check=lambda i, p: _check_qsgd_payload(layers[i], p))
+        return plan.qsgd_decode_bucketed(qd, width, level, d, torch.from_numpy(bn).to(dev)), plan
     norms = np.zeros(plan.nt, dtype=np.float32)
     for i, L in enumerate(layers):
         norms[i] = np.frombuffer(L.meta_tensor, dtype=np.float32).reshape(-1)[0]
@@ -935,6 +1018,9 @@ def _validate_layer(layer):
         _check_qsgd_fields(layer)  # the payload's size: checked as it is staged (_decode_qsgd_batch)
     elif ct == QSGD_PACKED_COMPRESSION_NAME:
         _check_packed_fields(layer)
+    elif ct == QSGD_BUCKETED_COMPRESSION_NAME:
+        _check_bucketed_fields(layer)
+        _check_qsgd_payload(layer, layer.values_data)  # here too (one more copy of the payload), and as it is staged
     else:
         raise ValueError(f"Unsupported compression_type={ct!r}")
     return None
@@ -942,13 +1028,16 @@ def _validate_layer(layer):
 
 def _scan_layers(proto_layers):
     """Validate every layer in message order.  Returns the QSGD layers grouped by (type, width,
-    level) and the Top-K layers with their payloads ``[(layer, values, indices, k)]``."""
+    level; bucketed layers also by their bucket size) and the Top-K layers with their payloads
+    ``[(layer, values, indices, k)]``."""
     groups: Dict[tuple, list] = {}
     topk: List[tuple] = []
     for L in proto_layers:
         got = _validate_layer(L)
         if got is not None:
             topk.append((L, *got))
+        elif L.compression_type == QSGD_BUCKETED_COMPRESSION_NAME:
+            groups.setdefault((L.compression_type, L.width, L.level, int(L.param_shape[0])), []).append(L)
         elif L.compression_type in _QSGD_TYPES:
             groups.setdefault((L.compression_type, L.width, L.level), []).append(L)
     return groups, topk

@@ -43,6 +43,10 @@ QSGD_COMPRESSION_NAME = "QSGDQuantCompression"
 # Opt-in bit-packed wire (not reference-compatible): codes q + L in
 # ceil(log2(2L+1)) bits instead of int8/int32 levels (include/omf_codec.h omf_qsgd_pack).
 QSGD_PACKED_COMPRESSION_NAME = "QSGDBitPackedCompression"
+# Opt-in bucket norms (QSGD §3.3; not reference-compatible): the plain layer's int8 / int32 levels, each
+# bucket of d consecutive elements quantised against its own norm (include/omf_codec.h
+# omf_qsgd_encode_bucketed); meta_tensor holds the tensor's ceil(n / d) norms, param_shape = [d].
+QSGD_BUCKETED_COMPRESSION_NAME = "QSGDBucketedCompression"
 
 
 def should_compress_tensor(x: torch.Tensor) -> bool:
@@ -90,6 +94,21 @@ def _arena(flats: Sequence[torch.Tensor], dev: torch.device, plan) -> torch.Tens
         if plan.arena_end >= H16_GATHER_MIN_ELEMS:
             return gather_arena(flats, dev, plan, dt)
     return gather_arena(flats, dev, plan)
+
+
+def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: int, dev: torch.device,
+                    call_index: int = 0, alpha: float = 1.0, key: int = 0):
+    """Encode flat fp32 tensors with bucket norms in ONE launch (``Plan.qsgd_encode_bucketed``, on-device
+    draws): ``(plan, q_arena, bnorms_dev)``, tensor k's norms at ``plan.bucket_layout(bucket_size)[0][k]``.
+    A bf16 / fp16 tensor raises ``ValueError`` (fp32 arenas only)."""
+    for f in flats:
+        if f.dtype != torch.float32:
+            raise ValueError(f"bucketed QSGD encodes float32 tensors, not {f.dtype}")
+    plan = codec.Plan.get([int(f.numel()) for f in flats], device=dev)
+    x = gather_arena(flats, dev, plan)
+    q, bn = plan.qsgd_encode_bucketed(x, int(bit_width), bucket_size, alpha=alpha, seed=int(key) & (2**64 - 1),
+                                      offset=call_index)
+    return plan, q, bn
 
 
 def encode_groups(flats: Sequence[torch.Tensor], bit_width: int, dev: torch.device, rng: str = "philox",
@@ -193,13 +212,23 @@ def philox_key(instance: int, client: int = 0) -> int:
 class QSGDQuantCompression(Compression):
     """QSGD (Alistarh et al., 2017), Algorithm 1 — on the GPU."""
 
-    def __init__(self, bit_width: int = 8, device="cpu", rng: str = "philox", packed_wire: bool = False):
+    def __init__(self, bit_width: int = 8, device="cpu", rng: str = "philox", packed_wire: bool = False,
+                 bucket_size: Optional[int] = None):
         super().__init__()
         self.s = int(bit_width)
         self.packed_wire = bool(packed_wire)  # encode_updates_dict / encode_layer_state emit packed layers
         self.device = torch.device(device)
         if rng not in ("philox", "mt19937"):
             raise ValueError(f"unknown rng={rng!r}; expected 'philox' or 'mt19937'")
+        # opt-in bucket norms (QSGDBucketedCompression layers): fp32 tensors, on-device draws, the int8 / int32
+        # levels; the reference has no buckets, so neither its stream (mt19937) nor the packed wire applies
+        self.bucket_size = None if bucket_size is None else int(bucket_size)
+        if self.bucket_size is not None:
+            codec.bucket_layout([], self.bucket_size)  # ValueError for a size that is not allowed
+            if self.packed_wire:
+                raise ValueError("bucket_size and packed_wire=True cannot be combined (no packed bucketed wire)")
+            if rng == "mt19937":
+                raise ValueError("bucket_size and rng='mt19937' cannot be combined (the reference has no buckets)")
         self.rng = rng
         self._calls = 0
         self._instance = next(_INSTANCES)
@@ -237,9 +266,19 @@ class QSGDQuantCompression(Compression):
             # levels = 2**s must fit LayerState.level (int32); the reference fails there too.
             raise ValueError(f"QSGD bit_width={self.s} out of range [0, 30]")
         dev = compute_device(flats[0], self.device)
-        groups = encode_groups(flats, self.s, dev, self.rng, self._next_call(), alpha=alpha, key=self.philox_key())
         levels = 2**self.s
         width, _ = choose_qsgd_storage_width(levels)
+        if self.bucket_size is not None:  # norm: the tensor's bucket norms, a 1-D fp32 CPU tensor
+            plan, q, bn = encode_bucketed(flats, self.s, self.bucket_size, dev, self._next_call(), alpha=alpha,
+                                          key=self.philox_key())
+            host = bn.cpu()  # synchronises the stream
+            boff, nb = plan.bucket_layout(self.bucket_size)
+            res: List[Tuple] = []
+            for o, n, b0, b1 in zip(plan.offsets, plan.sizes, boff, boff[1:] + [nb]):
+                mine = host[b0:b1].clone()
+                res.append((None, -1, -1, -1) if not bool(mine.any()) else (q[o:o + n], mine, width, levels))
+            return res
+        groups = encode_groups(flats, self.s, dev, self.rng, self._next_call(), alpha=alpha, key=self.philox_key())
         out: List[Tuple] = [None] * len(flats)
         for plan, q, norms, idx in groups:
             host_norms = norms.cpu().tolist()  # synchronises the stream
@@ -262,9 +301,11 @@ class QSGDQuantCompression(Compression):
         return self._do_compress(tensor)
 
     @staticmethod
-    def decompress_quantized(signed_levels: torch.Tensor, norm: float, levels: int, shape) -> torch.Tensor:
-        """qsgd.py:84-96: ``norm * signed_level / levels`` (fp32), on the GPU."""
-        if levels <= 0 or norm is None or norm == -1:
+    def decompress_quantized(signed_levels: torch.Tensor, norm, levels: int, shape,
+                             bucket_size: Optional[int] = None) -> torch.Tensor:
+        """qsgd.py:84-96: ``norm * signed_level / levels`` (fp32), on the GPU.  ``bucket_size`` (ours): ``norm``
+        is the tensor's 1-D fp32 bucket norms, as a bucketed ``compress`` returns them."""
+        if levels <= 0 or norm is None or (not isinstance(norm, torch.Tensor) and norm == -1):
             return signed_levels
         out_dev = signed_levels.device
         dev = compute_device(signed_levels, torch.device("cpu"))
@@ -283,12 +324,20 @@ class QSGDQuantCompression(Compression):
         if qbuf.device != dev or not qbuf.is_contiguous() or qbuf.data_ptr() % 16:
             qbuf = torch.empty(n, dtype=flat.dtype, device=dev)  # fresh allocations are 256-B aligned
             qbuf.copy_(flat)
+        if bucket_size is not None:
+            _, nb = plan.bucket_layout(bucket_size)
+            bn = torch.as_tensor(norm, dtype=torch.float32).reshape(-1)
+            if bn.numel() != nb:
+                raise ValueError(f"{bn.numel()} bucket norms for {n} elements in buckets of {bucket_size}: expected {nb}")
+            y = plan.qsgd_decode_bucketed(qbuf, width, int(levels), bucket_size, bn.to(dev).contiguous())
+            return y[:n].reshape(shape).to(out_dev)
         nrm = torch.tensor([float(norm)], dtype=torch.float32, device=dev)
         y = plan.qsgd_decode(qbuf, width, int(levels), nrm)
         return y[:n].reshape(shape).to(out_dev)
 
     def decompress(self, tensors, ctx):
-        """qsgd.py:98-107; ``ctx = (norm, width, levels, shape)``."""
+        """qsgd.py:98-107; ``ctx = (norm, width, levels, shape)`` (``norm``: the bucket norms of a compressor
+        with ``bucket_size``)."""
         norm, _width, levels, shape = ctx
         signed_levels = tensors[0] if isinstance(tensors, (tuple, list)) else tensors
-        return self.decompress_quantized(signed_levels, norm, levels, shape)
+        return self.decompress_quantized(signed_levels, norm, levels, shape, bucket_size=self.bucket_size)

@@ -90,6 +90,11 @@ class GpuOps:
         """Σ_k decode(qs[k], norms[k]) in list order (from ``y`` when ``init``), ``/ divisor``: one pass."""
         return self.plan.qsgd_decode_sum(qs, width, levels, norms, y_out=y, init=init, divisor=divisor)
 
+    def decode_sum_bucketed(self, qs, width, levels, bucket_size, bnorms, y, init, divisor):
+        """``decode_sum`` over bucketed payloads (``bnorms[k]``: client k's bucket-norm arena): one pass."""
+        return self.plan.qsgd_decode_sum_bucketed(qs, width, levels, bucket_size, bnorms, y_out=y, init=init,
+                                                  divisor=divisor)
+
     def decode_sum_packed(self, packed_list, levels, norms, y, init, divisor):
         """``decode_sum`` over packed arenas (the opt-in bit-packed wire): one pass, same bytes."""
         return self.plan.qsgd_decode_sum_packed(packed_list, levels, norms, y_out=y, init=init, divisor=divisor)
@@ -169,12 +174,14 @@ class DeviceAggregator:
         one level restored, on the device as they are staged); plain mixed with either raises ValueError.
         ``packed``: the update's QSGD layers are ``QSGDBitPackedCompression`` ones, ``payload`` is the
         packed arena (``qsgd_pack``'s layout, tensor t at byte ``offsets[t] * b / 8``) and ``width`` the
-        code's bits; an update's QSGD layers are all packed or all plain."""
+        code's bits; an update's QSGD layers are all packed or all plain.  ``QSGDBucketedCompression`` layers
+        (one bucket size per update, never mixed with the other two) give ``packed = ("bucket", d)`` and
+        ``norms`` the plan's bucket-norm arena."""
         from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
                                                                   _validate_layer, check_topk_indices, stage_topk)
         from .hybrid.communicator.global_grpc_compression import QuantValues
-        from .hybrid.compression import (QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME,
-                                         TOPK_QUANT_COMPRESSION_NAME)
+        from .hybrid.compression import (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME,
+                                         TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
 
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
@@ -187,9 +194,10 @@ class DeviceAggregator:
                 topk_payload[L.layer_name] = got
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
         packed_topk = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
-        known = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, "TopKCompression", *packed_topk, "")
-        qsgd = [L for L in kept if L.compression_type in known[:2]]
-        topk = [L for L in kept if L.compression_type in known[2:5]]
+        qsgd_types = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME)
+        known = (*qsgd_types, "TopKCompression", *packed_topk, "")
+        qsgd = [L for L in kept if L.compression_type in qsgd_types]
+        topk = [L for L in kept if L.compression_type in known[3:6]]
         dense = [L for L in kept if L.compression_type == ""]
         if any(L.compression_type not in known for L in kept):
             bad = next(L for L in kept if L.compression_type not in known)
@@ -199,18 +207,32 @@ class DeviceAggregator:
         if qsgd:
             width, level = qsgd[0].width, qsgd[0].level
             packed = qsgd[0].compression_type == QSGD_PACKED_COMPRESSION_NAME  # width: the code's bits
-            if any(L.width != width or L.level != level or (L.compression_type == QSGD_PACKED_COMPRESSION_NAME) != packed
-                   for L in qsgd):
+            if qsgd[0].compression_type == QSGD_BUCKETED_COMPRESSION_NAME:  # the wire's marker: ("bucket", d)
+                packed = ("bucket", int(qsgd[0].param_shape[0]))
+            if any(L.compression_type != qsgd[0].compression_type
+                   or (isinstance(packed, tuple) and int(L.param_shape[0]) != packed[1]) for L in qsgd):
+                raise ValueError("mixed QSGD width/level within one update (one wire per update: plain, bit-packed "
+                                 "or bucketed of one bucket size)")
+            if any(L.width != width or L.level != level for L in qsgd):
                 raise ValueError("mixed QSGD width/level within one update")
-            norms = np.zeros(self.plan.nt, dtype=np.float32)  # absent tensors: norm 0 adds +0
+            bucketed = isinstance(packed, tuple)
+            boff, nb = self.plan.bucket_layout(packed[1]) if bucketed else (None, self.plan.nt)
+            norms = np.zeros(nb, dtype=np.float32)  # absent tensors: norm 0 adds +0
             items = []
             for L in qsgd:
                 i = self.index[L.layer_name]
-                norms[i] = np.frombuffer(L.meta_tensor, dtype=np.float32).reshape(-1)[0]
+                if bucketed:  # the tensor's bucket norms (their count checked against the layer's own shape)
+                    bn = np.frombuffer(L.meta_tensor, dtype=np.float32)
+                    if bn.size != -(-self.plan.sizes[i] // packed[1]):
+                        raise ValueError(f"bucketed QSGD layer {L.layer_name!r}: {bn.size} bucket norms, expected "
+                                         f"{-(-self.plan.sizes[i] // packed[1])}")
+                    norms[boff[i]:boff[i] + bn.size] = bn
+                else:
+                    norms[i] = np.frombuffer(L.meta_tensor, dtype=np.float32).reshape(-1)[0]
                 # plain: tensor t at byte offsets[t] * width / 8; packed: at offsets[t] * b / 8 (qsgd_pack's arena)
                 items.append((self.plan.offsets[i] * width // 8, (lambda L=L: L.values_data)))
 
-            if packed:
+            if packed is True:
                 def check(k, payload):
                     _check_qsgd_payload(qsgd[k], payload)  # against the layer's own shape
                     n = self.plan.sizes[self.index[qsgd[k].layer_name]]
@@ -288,8 +310,10 @@ class DeviceAggregator:
             # Tensors absent from this update keep acc += (0 * q)/L = +0 (whatever q holds there:
             # any int8 / int32 level times a zero norm is a zero).
             qd, width, level, nd, packed = q_args
-            if packed:
+            if packed is True:
                 self.plan.qsgd_decode_packed(qd, level, nd, y_out=self.acc, accumulate=True)
+            elif packed:  # ("bucket", d)
+                self.plan.qsgd_decode_bucketed(qd, width, level, packed[1], nd, y_out=self.acc, accumulate=True)
             else:
                 self.plan.qsgd_decode(qd, width, level, nd, y_out=self.acc, accumulate=True)
         if t_args is not None:
@@ -308,7 +332,8 @@ class DeviceAggregator:
         ``qsgd_decode_sum(init=True)`` over their staged payload arenas (omf_qsgd_decode_sum: faster than
         the per-update decode at every run length measured).  Updates on the packed wire
         form runs of their own, by level, applied by ONE ``qsgd_decode_sum_packed(init=True)`` (measured
-        the same way); a plain run and a packed run never merge.  An update that also holds Top-K
+        the same way), bucketed updates runs by ``(width, level, bucket size)`` applied by ONE
+        ``qsgd_decode_sum_bucketed(init=True)``; runs of different wires never merge.  An update that also holds Top-K
         or dense layers ends the run and is applied as ``accumulate_layers`` applies it.  If staging
         update j raises, the updates before it are applied and counted, then the exception propagates:
         the accumulator holds exactly what j - 1 ``accumulate_layers`` calls would have left.  Same
@@ -323,9 +348,12 @@ class DeviceAggregator:
             if not batch:
                 return
             _, width, level, _, packed = batch[0][0]
-            if packed:
+            if packed is True:
                 self.plan.qsgd_decode_sum_packed([b[0][0] for b in batch], level, [b[0][3] for b in batch],
                                                  y_out=self.acc, init=True)
+            elif packed:  # ("bucket", d): a run shares (width, level, d)
+                self.plan.qsgd_decode_sum_bucketed([b[0][0] for b in batch], width, level, packed[1],
+                                                   [b[0][3] for b in batch], y_out=self.acc, init=True)
             else:
                 self.plan.qsgd_decode_sum([b[0][0] for b in batch], width, level, [b[0][3] for b in batch],
                                           y_out=self.acc, init=True)
@@ -358,6 +386,7 @@ class DeviceAggregator:
         self._check_fresh()
         names = [n for n in self.names if n in updates]
         if (not isinstance(compressor, QSGDQuantCompression) or compressor.packed_wire
+                or compressor.bucket_size is not None  # bucket norms: the wire path's bucketed encode and decode
                 or not all(should_compress_tensor(updates[n]) and updates[n].dtype == torch.float32 for n in names)
                 or [n for n in updates if n not in self.index]):
             from .hybrid.communicator.global_grpc_compression import encode_updates_dict
@@ -409,6 +438,7 @@ class DeviceAggregator:
         if self.avg is None:
             self.avg = torch.empty_like(self.acc)
         if (not isinstance(compressor, QSGDQuantCompression) or not self.compute_mean
+                or compressor.bucket_size is not None  # bucket norms: divide, then the bucketed encode
                 or compressor.rng != "philox"):  # parity mode draws MT19937 uniforms on the host
             self.avg.copy_(self.acc)
             if self.compute_mean:
@@ -458,7 +488,7 @@ class DeviceAggregator:
                 last[L.layer_name] = L
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])
         fusable = (isinstance(compressor, QSGDQuantCompression) and compressor.rng == "philox" and self.compute_mean
-                   and not compressor.packed_wire and kept
+                   and not compressor.packed_wire and compressor.bucket_size is None and kept
                    and all(L.compression_type == "QSGDQuantCompression" for L in kept)
                    and len({(L.width, L.level) for L in kept}) == 1)
         if not fusable:

@@ -1,0 +1,275 @@
+"""QSGD with bucket norms (omf_qsgd_*_bucketed): the single-read encoder, the decoder and the K-client sum,
+held to the CPU oracle bucket by bucket, and the public path through the wire layer and the PS aggregator.
+
+One plan per bucket size d with tensors at the sizes the bucket mapping can get wrong (less than a quad, one
+less / exactly / one more than a bucket, a partial last bucket, one less / exactly / more than a 4 Ki block and
+a 16 Ki item), an all-zero bucket, a bucket with one non-zero element, canaries in the padding and around the
+outputs.  The norm bound is derived: any fp32 summation order of d non-negative squares has relative error
+<= d 2^-24, the square root halves it and rounds once more: (d + 4) 2^-25."""
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from omnifed_amd import codec
+from omnifed_amd.hybrid.communicator.global_grpc_compression import (build_global_compressor, decode_layer_tensor,
+                                                                     decode_updates_dict, decode_updates_into,
+                                                                     encode_layer_state, encode_updates_dict)
+from omnifed_amd.hybrid.compression import QSGD_BUCKETED_COMPRESSION_NAME
+from omnifed_amd.ps import DeviceAggregator
+
+pytestmark = pytest.mark.gpu
+
+SIZES = (64, 256, 1024, 4096)
+SEED, OFF = 0xB0C, 3
+GUARD = 64
+CANARY = 3e4
+
+
+def _sizes(d):
+    return [1, 3, d - 1, d, d + 1, 2 * d + 5, 4095, 4096, 4096 + d + 1, 16384 - 1, 16384 + d // 2 + 3]
+
+
+@pytest.fixture(scope="module")
+def arenas(gpu):
+    """d -> (plan, x, mask, bidx): the canary-padded arena, the mask of its tensors' elements and every
+    element's index into the bucket-norm arena."""
+    out = {}
+    for d in SIZES:
+        sizes = _sizes(d)
+        plan = codec.Plan(sizes, device=gpu)
+        boff, nb = plan.bucket_layout(d)
+        g = torch.Generator(device=gpu).manual_seed(d)
+        x = torch.full((plan.arena_end,), CANARY, device=gpu)
+        mask = torch.zeros(plan.arena_end, dtype=torch.bool)
+        bidx = np.zeros(plan.arena_end, dtype=np.int64)
+        for o, n, b in zip(plan.offsets, sizes, boff):
+            x[o:o + n] = torch.randn(n, device=gpu, generator=g) * 1e-3
+            mask[o:o + n] = True
+            bidx[o:o + n] = b + np.arange(n) // d
+        o = plan.offsets[5]  # 2 d + 5 elements: bucket 0 all zero, bucket 1 one non-zero element
+        x[o:o + 2 * d] = 0.0
+        x[o + d + 7] = -2.5e-3
+        out[d] = (plan, x, mask, bidx)
+    return out
+
+
+ENC_CASES = [(s, alpha, draws) for s, alpha in ((4, 1.0), (3, 3.0), (8, 1.0)) for draws in ("philox", "u")]
+ENC_CASES.append((4, 1.0, "bnorm_in"))
+
+
+@pytest.mark.parametrize("s,alpha,draws", ENC_CASES)
+@pytest.mark.parametrize("d", SIZES)
+def test_bucketed_encode_equals_oracle_per_bucket(gpu, arenas, d, s, alpha, draws):
+    plan, x, mask, bidx = arenas[d]
+    boff, nb = plan.bucket_layout(d)
+    x_before = x.clone()
+    L, width = 2 ** s, codec.storage_width(2 ** s)
+    kw = {"alpha": alpha, "seed": SEED, "offset": OFF}
+    if draws == "u":
+        kw["u"] = torch.rand(plan.arena_end, device=gpu, generator=torch.Generator(device=gpu).manual_seed(7))
+    if draws == "bnorm_in":
+        kw["bnorm_in"] = plan.qsgd_norms_bucketed(x, d, alpha=alpha) * 1.25
+    np_q = plan.payload_elems(width)
+    qbuf = torch.full((np_q + 2 * GUARD,), 0x55, dtype=torch.int8 if width == 8 else torch.int32, device=gpu)
+    nbuf = torch.full((nb + 2 * GUARD,), -7.0, device=gpu)
+    q, bn = plan.qsgd_encode_bucketed(x, s, d, q_out=qbuf[GUARD:GUARD + np_q], bnorm_out=nbuf[GUARD:GUARD + nb], **kw)
+    assert plan.last_encoder == "bucketed"
+    torch.cuda.synchronize()
+    # nothing outside the tensors is written, the arena is only read
+    m = mask.to(gpu)
+    assert bool((q[:plan.arena_end][~m] == 0x55).all())
+    assert bool((qbuf[:GUARD] == 0x55).all()) and bool((qbuf[GUARD + plan.arena_end:] == 0x55).all())
+    assert bool((nbuf[:GUARD] == -7.0).all()) and bool((nbuf[GUARD + nb:] == -7.0).all())
+    assert torch.equal(x.view(torch.int32), x_before.view(torch.int32))
+    xs = x.cpu() * torch.tensor(alpha, dtype=torch.float32)  # fl32(alpha x)
+    bn_h, q_h = bn.cpu(), q.cpu()
+    if draws == "bnorm_in":
+        assert torch.equal(bn_h.view(torch.int32), kw["bnorm_in"].cpu().view(torch.int32))
+    else:
+        assert torch.equal(plan.qsgd_norms_bucketed(x, d, alpha=alpha).view(torch.int32), bn.view(torch.int32))
+    y = plan.qsgd_decode_bucketed(q, width, L, d, bn).cpu()
+    for t, (o, n) in enumerate(zip(plan.offsets, plan.sizes)):
+        u = kw["u"].cpu()[o:o + n] if "u" in kw else torch.from_numpy(oracle.philox_uniforms(SEED, OFF, t, n))
+        for j in range(-(-n // d)):
+            lo, hi = o + j * d, o + min((j + 1) * d, n)
+            v, norm = xs[lo:hi], float(bn_h[boff[t] + j])
+            if draws != "bnorm_in":
+                exact = float(np.sqrt(np.sum(v.double().numpy() ** 2)))
+                assert abs(norm - exact) <= (d + 4) * 2.0 ** -25 * exact, (t, j, norm, exact)
+            want, *_ = oracle.qsgd_quantize(v, s, norm=norm, u=u[lo - o:hi - o])
+            assert torch.equal(q_h[lo:hi].long(), want.long()), (t, j)
+            dec = oracle.qsgd_dequantize(want, norm, L, v.shape)
+            assert torch.equal(y[lo:hi].view(torch.int32), dec.float().view(torch.int32)), (t, j)
+
+
+@pytest.mark.parametrize("rows,static_d", ((8, False), (16, False), (4, False)))
+@pytest.mark.parametrize("d", SIZES)
+def test_encoder_variants_give_the_default_bits(gpu, arenas, d, rows, static_d):
+    plan, x, mask, _ = arenas[d]
+    q, bn = plan.qsgd_encode_bucketed(x, 4, d, alpha=3.0, seed=SEED, offset=OFF)
+    try:
+        plan.set_bucket_rows(rows, static_d)
+        q2, bn2 = plan.qsgd_encode_bucketed(x, 4, d, alpha=3.0, seed=SEED, offset=OFF)
+    finally:
+        plan.set_bucket_rows(4)
+    m = mask.to(gpu)
+    assert torch.equal(bn.view(torch.int32), bn2.view(torch.int32))
+    assert torch.equal(q[:plan.arena_end][m], q2[:plan.arena_end][m])
+
+
+@pytest.mark.parametrize("d", SIZES)
+def test_bucket_norm_bits_do_not_depend_on_the_offset(gpu, arenas, d):
+    plan, x, _, _ = arenas[d]
+    boff, nb = plan.bucket_layout(d)
+    bn = plan.qsgd_norms_bucketed(x, d)
+    for t in (5, 8, 10):  # partial last buckets, below and above one item
+        o, n = plan.offsets[t], plan.sizes[t]
+        other = codec.Plan([4096 + 9, n, 5], device=gpu)
+        x2 = torch.full((other.arena_end,), CANARY, device=gpu)
+        x2[other.offsets[1]:other.offsets[1] + n] = x[o:o + n]
+        b2, _ = other.bucket_layout(d)
+        got = other.qsgd_norms_bucketed(x2, d)[b2[1]:b2[2]]
+        assert torch.equal(got.view(torch.int32), bn[boff[t]:boff[t] + -(-n // d)].view(torch.int32))
+
+
+def _message(plan, d, gpu, width, L, seed):
+    """A payload no encoder made: levels uniform in [-L, L], bucket norms with zeros and infinities."""
+    g = torch.Generator(device=gpu).manual_seed(seed)
+    _, nb = plan.bucket_layout(d)
+    q = torch.randint(-L, L + 1, (plan.payload_elems(width),), device=gpu, generator=g,
+                      dtype=torch.int32).to(torch.int8 if width == 8 else torch.int32)
+    bn = torch.rand(nb, device=gpu, generator=g) * 4.0
+    bn[::7] = 0.0
+    bn[3::11] = float("inf")
+    return q, bn
+
+
+def _decode_np(q, bn, bidx, L):
+    with np.errstate(invalid="ignore", over="ignore"):
+        n = bidx.size
+        return ((bn.cpu().numpy()[bidx] * q.cpu().numpy()[:n].astype(np.float32)).astype(np.float32)
+                / np.float32(L)).astype(np.float32)
+
+
+@pytest.mark.parametrize("accumulate", (False, True))
+@pytest.mark.parametrize("width,L", ((8, 16), (8, 100), (32, 256)))
+@pytest.mark.parametrize("d", SIZES)
+def test_bucketed_decode_of_foreign_messages(gpu, arenas, d, width, L, accumulate):
+    plan, x, mask, bidx = arenas[d]
+    q, bn = _message(plan, d, gpu, width, L, 11)
+    y0 = torch.full((plan.arena_end + GUARD,), 0.375, device=gpu)
+    y = y0.clone()
+    plan.qsgd_decode_bucketed(q, width, L, d, bn, y_out=y[:plan.arena_end], accumulate=accumulate)
+    want = _decode_np(q, bn, bidx, L)
+    if accumulate:
+        with np.errstate(invalid="ignore"):
+            want = np.float32(0.375) + want
+    want = np.where(mask.numpy(), want, np.float32(0.375))  # padding keeps its bytes
+    got = y.cpu().numpy()
+    assert np.array_equal(got[:plan.arena_end], want, equal_nan=True)
+    assert (got[plan.arena_end:] == 0.375).all()
+
+
+@pytest.mark.parametrize("divisor", (None, 7.0))
+@pytest.mark.parametrize("init", (False, True))
+@pytest.mark.parametrize("K", (1, 3, 9))
+@pytest.mark.parametrize("d,width,L", ((64, 8, 16), (1024, 32, 256), (4096, 8, 100)))
+def test_bucketed_decode_sum_is_the_sequential_sum(gpu, arenas, d, width, L, K, init, divisor):
+    plan, x, mask, bidx = arenas[d]
+    msgs = [_message(plan, d, gpu, width, L, 20 + k) for k in range(K)]
+    for _, bn in msgs:
+        bn[3::11] = 0.5  # finite terms: the sum's order is what is checked
+    y = torch.full((plan.arena_end + GUARD,), 0.375, device=gpu)
+    plan.qsgd_decode_sum_bucketed([m[0] for m in msgs], width, L, d, [m[1] for m in msgs], y_out=y[:plan.arena_end],
+                                  init=init, divisor=divisor)
+    s = np.full(plan.arena_end, 0.375 if init else 0.0, dtype=np.float32)
+    for q, bn in msgs:
+        s = (s + _decode_np(q, bn, bidx, L)).astype(np.float32)
+    if divisor is not None:
+        s = (s / np.float32(divisor)).astype(np.float32)
+    pad = np.float32(0.375) if init else np.float32(0.0)  # init: padding kept; else written (+0 / divisor)
+    want = np.where(mask.numpy(), s, pad)
+    got = y.cpu().numpy()
+    assert np.array_equal(got[:plan.arena_end].view(np.int32), want.view(np.int32))
+    assert (got[plan.arena_end:] == 0.375).all()
+
+
+def test_public_path_wire_and_aggregator(gpu):
+    d, s = 256, 4
+    shapes = {"w": (37, 129), "zero": (300,), "b": (1000,)}
+    comps = [build_global_compressor(enabled=True, scheme="qsgd", bit_width=s, bucket_size=d, device=gpu)
+             for _ in range(3)]
+    g = torch.Generator(device=gpu).manual_seed(5)
+    decoded, updates = [], []
+    for c, comp in enumerate(comps):
+        comp.client_id = c
+        upd = {k: torch.randn(sh, device=gpu, generator=g) * 1e-3 for k, sh in shapes.items()}
+        upd["zero"].zero_()
+        layers = encode_updates_dict(upd, comp)
+        assert [L.compression_type for L in layers] == [QSGD_BUCKETED_COMPRESSION_NAME, "", QSGD_BUCKETED_COMPRESSION_NAME]
+        for L in (layers[0], layers[2]):
+            n = int(np.prod(shapes[L.layer_name]))
+            assert (list(L.param_shape), L.width, L.level, L.values_dtype) == ([d], 8, 16, "torch.int8")
+            assert list(L.original_shape) == list(shapes[L.layer_name])
+            assert len(L.values_data) == n and len(L.meta_tensor) == 4 * -(-n // d)
+        dec = decode_updates_dict(layers, device=gpu)
+        for L in (layers[0], layers[2]):  # the oracle's decode of the wire's levels, bucket by bucket
+            q = torch.from_numpy(np.frombuffer(L.values_data, dtype=np.int8).copy())
+            bn = np.frombuffer(L.meta_tensor, dtype=np.float32)
+            want = torch.cat([oracle.qsgd_dequantize(q[j * d:(j + 1) * d], float(bn[j]), 16, (-1,)).float()
+                              for j in range(bn.size)])
+            assert torch.equal(dec[L.layer_name].cpu().reshape(-1).view(torch.int32), want.view(torch.int32))
+            assert float(np.abs(bn).max()) > 0
+        assert not bool(dec["zero"].any())
+        decoded.append(dec)
+        updates.append((layers, 10 + c))
+    agg = DeviceAggregator(list(shapes.items()), device=gpu)
+    agg.accumulate_many(updates)
+    assert agg.update_count == 3 and agg.total_samples == 33
+    for i, name in enumerate(shapes):
+        o, n = agg.plan.offsets[i], agg.plan.sizes[i]
+        want = torch.zeros(n, device=gpu)
+        for dec in decoded:
+            want = want + dec[name].reshape(-1)
+        assert torch.equal(agg.acc[o:o + n].view(torch.int32), want.view(torch.int32))
+    # without the dense layers the three updates are one run: a single qsgd_decode_sum_bucketed, the same bytes
+    run = DeviceAggregator(list(shapes.items()), device=gpu)
+    run.accumulate_many([([L for L in layers if L.compression_type], ns) for layers, ns in updates])
+    assert torch.equal(run.acc.view(torch.int32), agg.acc.view(torch.int32))
+
+
+def test_single_tensor_entry_points_and_the_ps_downlink(gpu):
+    d, s = 128, 4
+    comp = build_global_compressor(enabled=True, scheme="qsgd", bit_width=s, bucket_size=d, device=gpu)
+    t = torch.randn(5, 77, device=gpu, generator=torch.Generator(device=gpu).manual_seed(9)) * 1e-3
+    # compress / decompress: the levels against the bucket norms, the oracle's decode per bucket
+    q, bn, width, L = comp.compress(t)
+    assert (tuple(q.shape), q.dtype, width, L) == ((5, 77), torch.int8, 8, 16)
+    assert bn.dtype == torch.float32 and tuple(bn.shape) == (-(-385 // d),)
+    want = torch.cat([oracle.qsgd_dequantize(q.cpu().reshape(-1)[j * d:(j + 1) * d], float(bn[j]), L, (-1,)).float()
+                      for j in range(bn.numel())]).reshape(5, 77)
+    for got in (comp.decompress(q, (bn, width, L, t.shape)),
+                comp.decompress_quantized(q, bn, L, t.shape, bucket_size=d)):
+        assert torch.equal(got.cpu().view(torch.int32), want.view(torch.int32))
+    assert float((want - t.cpu()).abs().max()) <= float(bn.max()) / L
+    # encode_layer_state -> decode_layer_tensor / decode_updates_into
+    layer = encode_layer_state("w", t, comp)
+    assert layer.compression_type == QSGD_BUCKETED_COMPRESSION_NAME and list(layer.param_shape) == [d]
+    dec = decode_layer_tensor(layer, device=gpu)
+    target = {"w": torch.zeros(5, 77, device=gpu)}
+    decode_updates_into([layer], target)
+    assert torch.equal(target["w"].view(torch.int32), dec.view(torch.int32))
+    assert float((dec - t).abs().max()) <= float(np.frombuffer(layer.meta_tensor, dtype=np.float32).max()) / L
+    # the PS with a bucketed compressor: the in-process client and the downlink stay on the bucketed wire
+    agg = DeviceAggregator([("w", (5, 77))], device=gpu)
+    agg.accumulate_updates({"w": t}, comp, number_samples=2, weight=2.0)
+    assert agg.plan.last_encoder == "bucketed"  # (the one-tensor plan is shared) not the per-tensor encoder
+    avg, layers = agg.apply_and_encode(comp)
+    assert [L_.compression_type for L_ in layers] == [QSGD_BUCKETED_COMPRESSION_NAME]
+    assert torch.equal(avg["w"].reshape(-1), agg.acc[:385] / 2) and bool(agg.acc[:385].any())
+    agg2 = DeviceAggregator([("w", (5, 77))], device=gpu)
+    _, down = agg2.accumulate_apply_encode([layer], 1, comp)
+    assert [L_.compression_type for L_ in down] == [QSGD_BUCKETED_COMPRESSION_NAME]
+    assert torch.equal(agg2.acc[:385].view(torch.int32), dec.reshape(-1).view(torch.int32))
