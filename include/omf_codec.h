@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 119
+#define OMF_ABI_VERSION 120
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -132,7 +132,8 @@ int omf_plan_set_encode_strategy(omf_plan* plan, int32_t strategy);
 int32_t omf_plan_encode_strategy(const omf_plan* plan);
 /* The encoder the plan's latest encode (or fused PS step) launched: 0 register-resident +
  * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in),
- * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed), 8 the
+ * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -372,6 +373,37 @@ int omf_qsgd_decode_packed(omf_plan* plan, const uint32_t* packed, int32_t level
 int omf_qsgd_decode_sum_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* norm,
                                int32_t nclients, int32_t levels, float* y_out, int32_t init, float divisor,
                                void* stream);
+
+/*
+ * Opt-in bucketed QSGD on the bit-packed wire ("QSGDBucketedPackedCompression"; NOT reference-compatible): the
+ * product of the two wires above, no new rule.  Norms: omf_qsgd_encode_bucketed's (bucket_size, the
+ * bucket-norm arena, the same bits).  Codes: omf_qsgd_pack's arena (code q + L in b = omf_qsgd_packed_bits(L)
+ * bits, LSB first, tensor t at word offsets[t] * b / 32 of ceil(arena_end / 32) * b words, code 0 after a
+ * tensor's last element inside its last group, groups without a tensor element not written); every tensor
+ * offset a multiple of 32 elements, else OMF_EINVAL.  fp32 arenas only.
+ *   omf_qsgd_encode_bucketed_packed      ONE launch that reads x once and writes the words that
+ *                                        omf_qsgd_encode_bucketed followed by omf_qsgd_pack writes (L =
+ *                                        2^bit_width, bit_width 0 .. 30, on every written group) and the norms
+ *                                        omf_qsgd_encode_bucketed writes; u, seed, offset, bnorm_in as there.
+ *                                        packed_out 8-byte aligned.  No in-kernel wait.
+ *   omf_qsgd_decode_bucketed_packed      the floats omf_qsgd_decode_bucketed gives on the unpacked levels
+ *                                        (accumulate: y_out += that); only the tensors' elements are written.
+ *   omf_qsgd_decode_sum_bucketed_packed  omf_qsgd_decode_sum_packed with a norm per bucket (bnorm: nclients
+ *                                        device pointers): the same order, padding fill, division and errors;
+ *                                        at most 8 clients per launch (4 for codes wider than 10 bits), more
+ *                                        are chained.
+ * levels: any 1 <= L < 2^31 - 1 on the receive side (a message no encoder made decodes by the rule, a code
+ * above 2 L included, as omf_qsgd_decode_packed).  OMF_EINVAL: a bad bucket_size, levels or bit_width, NULL or
+ * misaligned buffers, y_out overlapping a packed or norm buffer.
+ */
+int omf_qsgd_encode_bucketed_packed(omf_plan* plan, const float* x, float alpha, int32_t bit_width, int64_t bucket_size,
+                                    const float* u, uint64_t seed, uint64_t offset, const float* bnorm_in,
+                                    uint32_t* packed_out, float* bnorm_out, void* stream);
+int omf_qsgd_decode_bucketed_packed(omf_plan* plan, const uint32_t* packed, int32_t levels, int64_t bucket_size,
+                                    const float* bnorm, float* y_out, int32_t accumulate, void* stream);
+int omf_qsgd_decode_sum_bucketed_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* bnorm,
+                                        int32_t nclients, int32_t levels, int64_t bucket_size, float* y_out,
+                                        int32_t init, float divisor, void* stream);
 
 /*
  * Top-K sparsification with error feedback, all tensors of the plan in one call.

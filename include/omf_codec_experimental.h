@@ -68,6 +68,11 @@ int omf_plan_set_h16(omf_plan* plan, int32_t wide_loads, int32_t rows);
  * default: measured no slower at any bucket size, faster from 1024 up): the 4-row kernels with the bucket size
  * at compile time, else as a kernel argument (8 and 16 rows always).  Identical norms and payloads. */
 int omf_plan_set_bucket_rows(omf_plan* plan, int32_t rows, int32_t static_d);
+/* The packed bucketed encoder's output assignment (omf_qsgd_encode_bucketed_packed, code widths up to 16 bits;
+ * scripts/bucketed_packed_ab.py times them): 0 thread i of a workgroup writes words i, i + 256, ... of its
+ * block (lane-contiguous stores), 1 two threads per 32-element group, each writing half of the group's words.
+ * Identical norms and words. */
+int omf_plan_set_bucket_pack(omf_plan* plan, int32_t mode);
 /* Diagnostics of the last bracketed single-read encode (strategy 3; synchronises `stream`,
  * not for the hot path): out[0] tensors requantised whole (norm outside the sampled bracket,
  * a wave's undecided-quad slot overflowed, or a degenerate sample), out[1] of those the

@@ -284,10 +284,11 @@ class Plan:
     @property
     def last_encoder(self) -> str:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
-        "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms) or
-        "none"."""
+        "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms),
+        "bucketed_packed" (bucket norms, codes packed in the pass) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
-        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {5: "norm_in", 6: "h16", 7: "bucketed"}.get(code, "none")
+        return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {
+            5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -691,6 +692,104 @@ class Plan:
         1024 elements per workgroup.  Identical results."""
         with self._lock:
             check(lib().omf_plan_set_bucket_rows(self._h, int(rows), 1 if static_d else 0), "omf_plan_set_bucket_rows")
+
+    # ------------------------------------------------------------ bucket norms on the bit-packed wire (opt-in)
+    def qsgd_encode_bucketed_packed(self, x: torch.Tensor, bit_width: int, bucket_size: int,
+                                    packed_out: Optional[torch.Tensor] = None,
+                                    bnorm_out: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                                    u: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+                                    bnorm_in: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        """omf_qsgd_encode_bucketed_packed: ``qsgd_encode_bucketed`` whose codes leave the encode pass already
+        packed — the words of ``qsgd_pack(qsgd_encode_bucketed(...))`` on every written group, in one launch;
+        returns ``(packed, bnorms)``.  ``packed_out`` is written only where a tensor has elements.  fp32 arenas
+        only: a bf16 / fp16 ``x`` raises ``ValueError``."""
+        if getattr(x, "dtype", None) in H16_FORMATS:
+            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        _, nb = self.bucket_layout(bucket_size)
+        s = int(bit_width)
+        if not 0 <= s <= 30:
+            raise ValueError("bit_width must be in [0, 30]")
+        dev = self.device
+        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        words = self.packed_words(2 ** s)
+        if packed_out is None:
+            packed_out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+        _need(packed_out, "packed_out", torch.int32, dev, words, 8)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        if u is not None:
+            _need(u, "u", torch.float32, dev, self.arena_end, 16)
+        if bnorm_in is not None:
+            _need(bnorm_in, "bnorm_in", torch.float32, dev, nb, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_encode_bucketed_packed(self._h, _ptr(x), float(alpha), s, int(bucket_size), _ptr(u),
+                                                        int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                        int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(bnorm_in),
+                                                        _ptr(packed_out), _ptr(bnorm_out), ctypes.c_void_p(st)),
+                  "omf_qsgd_encode_bucketed_packed")
+        return packed_out, bnorm_out
+
+    def qsgd_decode_bucketed_packed(self, packed: torch.Tensor, levels: int, bucket_size: int, bnorm: torch.Tensor,
+                                    y_out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                                    stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_bucketed_packed: ``qsgd_decode_bucketed`` of a packed arena."""
+        levels = int(levels)
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        _need(packed, "packed", torch.int32, dev, self.packed_words(levels), 4)
+        _need(bnorm, "bnorm", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:  # the first call at a bucket size makes the plan's table
+            check(lib().omf_qsgd_decode_bucketed_packed(self._h, _ptr(packed), levels, int(bucket_size), _ptr(bnorm),
+                                                        _ptr(y_out), 1 if accumulate else 0, ctypes.c_void_p(st)),
+                  "omf_qsgd_decode_bucketed_packed")
+        return y_out
+
+    def qsgd_decode_sum_bucketed_packed(self, packed_list: Sequence[torch.Tensor], levels: int, bucket_size: int,
+                                        bnorms: Sequence[torch.Tensor], y_out: Optional[torch.Tensor] = None,
+                                        init: bool = False, divisor: Optional[float] = None,
+                                        stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_sum_bucketed_packed: ``qsgd_decode_sum_packed`` with ``bnorms[k]`` client k's
+        bucket-norm arena; the bytes of ``qsgd_decode_sum_bucketed`` on the levels unpacked."""
+        levels = int(levels)
+        packed_list, bnorms = list(packed_list), list(bnorms)
+        if not packed_list or len(packed_list) != len(bnorms):
+            raise ValueError("qsgd_decode_sum_bucketed_packed needs one norm arena per payload and at least one "
+                             f"({len(packed_list)}, {len(bnorms)})")
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        words = self.packed_words(levels)  # raises on levels outside the packed wire's range
+        for k, (p, nm) in enumerate(zip(packed_list, bnorms)):
+            _need(p, f"packed_list[{k}]", torch.int32, dev, words, 4)
+            _need(nm, f"bnorms[{k}]", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if init:
+                raise ValueError("init=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        n = len(packed_list)
+        pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in packed_list])
+        npp = (ctypes.c_void_p * n)(*[nm.data_ptr() for nm in bnorms])
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_decode_sum_bucketed_packed(self._h, pp, npp, n, levels, int(bucket_size),
+                                                            _ptr(y_out), 1 if init else 0, d, ctypes.c_void_p(st)),
+                  "omf_qsgd_decode_sum_bucketed_packed")
+        return y_out
+
+    def set_bucket_pack(self, mode: int = 0) -> None:
+        """Experiment hook of the packed bucketed encoder (omf_plan_set_bucket_pack): 0 (the default) thread i
+        writes words i, i + 256, ... of its block, 1 two threads per 32-element group.  Identical results."""
+        with self._lock:
+            check(lib().omf_plan_set_bucket_pack(self._h, int(mode)), "omf_plan_set_bucket_pack")
 
     # ------------------------------------------------------------ bit-packed wire (opt-in)
     def packed_words(self, levels: int) -> int:

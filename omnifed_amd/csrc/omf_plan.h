@@ -63,6 +63,7 @@ struct omf_plan {
   int64_t bucket_nb[7] = {0, 0, 0, 0, 0, 0, 0};
   int32_t bucket_rows = 4;
   bool bucket_static_d = true;   // the 4-row kernel with d at compile time (omf_plan_set_bucket_rows)
+  int32_t bucket_pack = 0;       // the packed bucketed encoder's output assignment (omf_plan_set_bucket_pack)
   // ---- the plan's block: one device allocation, carved by upload_plan (omf_qsgd.hip) in this order
   void* d_block = nullptr;
   uint8_t* d_sync = nullptr;    // [ticket u32, err u32, pad 8][counters u32 x nt, pad16][granules u64 x nt, pad16]
@@ -183,6 +184,33 @@ inline int plan_enter(omf_plan* p, hipStream_t st) {
 inline int plan_leave(omf_plan* p, hipStream_t st) {
   p->last_stream = st;
   p->last_valid = true;
+  return OMF_OK;
+}
+
+// The plan's arena as the bit-packed wires' kernels walk it (omf_qsgd_pack.hip, omf_qsgd_bucket_pack.hip).
+struct ArenaArgs {
+  const uint32_t* binfo;
+  int64_t nbinfo;
+  const int64_t* begins;
+  const int64_t* sizes;
+  int32_t nt;
+  int64_t arena_end;
+};
+
+// The plan's arena for a packed wire and its grid of workgroups of 32 * kThreads elements, or an error: every
+// tensor offset a multiple of 32 elements (a tensor's stream then starts on a word, and a 32-element group
+// lies in one tensor).
+inline int packed_arena(const omf_plan* plan, ArenaArgs* a, dim3* grid) {
+  for (const int64_t o : plan->offsets)
+    if (o & 31) return fail(OMF_EINVAL, "the packed wire needs tensor offsets that are multiples of 32 elements");
+  a->binfo = plan->d_dec_binfo;
+  a->nbinfo = plan->n_dec_blocks;
+  a->begins = plan->d_begins;
+  a->sizes = plan->d_sizes;
+  a->nt = plan->nt;
+  a->arena_end = plan->arena_end;
+  constexpr int64_t blk = 32 * kThreads;
+  *grid = dim3((unsigned)((a->arena_end + blk - 1) / blk));
   return OMF_OK;
 }
 

@@ -191,6 +191,7 @@ enum Encoder : int32_t {
   kEncCallerNorms = 5,  // levels with caller norms: one pass, no hand-off
   kEncH16 = 6,          // 16-bit arena (omf_qsgd_h16.hip): never choose_encoder's, the entry point's
   kEncBucketed = 7,     // bucket norms (omf_qsgd_bucketed.hip): never choose_encoder's, the entry point's
+  kEncBucketedPacked = 8,  // bucket norms, codes packed in the pass (omf_qsgd_bucket_pack.hip): the entry point's
 };
 
 struct Call {

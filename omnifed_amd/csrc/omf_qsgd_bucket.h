@@ -1,4 +1,4 @@
-// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip), one copy of each.  Not part of the
+// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip, omf_qsgd_bucket_pack.hip), one copy of each.  Not part of the
 // C ABI.  The host rules come first and are plain C++ with no HIP header; the device rules follow under
 // __HIPCC__.
 //
@@ -65,6 +65,8 @@ inline int64_t offsets(const int64_t* sizes, int32_t nt, int logd, int64_t* boff
 
 #ifdef __HIPCC__
 #include "omf_common.h"
+#include "omf_plan.h"
+#include "omf_qsgd_enc.h"
 
 namespace omf {
 namespace bucket {
@@ -130,4 +132,117 @@ __device__ __forceinline__ void bucket_sums(float (&s)[V], int logd, float (*xch
 
 }  // namespace bucket
 }  // namespace omf
+
+// ---------------------------------------------------------------- what the bucketed units share
+// (omf_qsgd_bucketed.hip: the int8 / int32 wire; omf_qsgd_bucket_pack.hip: the bit-packed wire).  In an
+// unnamed namespace, as the encoders' steps they build on are (omf_qsgd_enc.h).
+
+namespace {
+
+using namespace omf;
+
+constexpr const char* kBucketMisaligned = "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)";
+constexpr const char* kBucketBadSize = "bucket_size must be a power of two in [64, 4096]";
+
+// The front half of one block [b, end) of V rows of a tensor (begins at tbegin; its norms at nbase of the
+// bucket arena): x loaded once (non-temporal) and scaled into v, norm[k] the norm of the bucket that holds
+// this thread's quad of row k — computed (bucket_sums) or the caller's — and stored by the bucket's first
+// lane (of its first row).  Called by the whole workgroup.
+template <bool FULL, int V>
+__device__ __forceinline__ void bucket_front(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int64_t nbase,
+                                             int logd, float (*xch)[kWaves], float4 (&v)[V], float (&norm)[V]) {
+  const int tid = (int)threadIdx.x;
+  load_f4<V, FULL, true>(a.x, b, end, v);  // read once: non-temporal
+  scale_f4<V>(v, a);
+  const int64_t rel = (b - tbegin) + 4 * tid;  // this thread's row 0, from the tensor's begin
+  if (a.norm_in) {  // the caller's norms (uniform branch)
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const bool live = FULL || b + 4 * ((int64_t)k * kThreads + tid) < end;
+      norm[k] = live ? a.norm_in[nbase + ((rel + 1024 * k) >> logd)] : 0.0f;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) norm[k] = sq4(v[k], 0.0f);
+    bucket::bucket_sums<V>(norm, logd, xch);
+#pragma unroll
+    for (int k = 0; k < V; ++k) norm[k] = sqrtf(norm[k]);
+  }
+  // the bucket's first lane (of its first row) stores the norm
+  const int lane_mask = logd <= 10 ? (1 << (logd - 2)) - 1 : kThreads - 1;
+  const int row_mask = logd <= 10 ? 0 : (1 << (logd - 10)) - 1;
+  if ((tid & lane_mask) == 0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (k & row_mask) continue;
+      if (FULL || b + 4 * ((int64_t)k * kThreads + tid) < end) a.norm_out[nbase + ((rel + 1024 * k) >> logd)] = norm[k];
+    }
+  }
+}
+
+// Quantise V rows of the block at b against each row's own norm: quant_store (omf_qsgd_enc.h) with a norm per
+// row (the draws and the level math are its: philox_rows, load_quad, qsgd_quad).  sink(k, e, qq): the four
+// levels of the live quad (e < end) of row k at element e — the wire's store.
+template <bool HAS_U, bool FULL, int V, class Sink>
+__device__ __forceinline__ void quant_rows(const float4 (&v)[V], const EncArgs& a, int64_t b, int64_t end,
+                                           int64_t tbegin, int32_t tensor, const float (&norm)[V], Sink sink) {
+  static_assert(V % 4 == 0, "rows come in groups of 4 (RNG slots)");
+#pragma unroll
+  for (int g = 0; g < V / 4; ++g) {
+    float4 uu[4];
+    if (HAS_U) {
+#pragma unroll
+      for (int sl = 0; sl < 4; ++sl)
+        uu[sl] = load_quad<FULL>(a.u, b + 4 * ((int64_t)(4 * g + sl) * kThreads + threadIdx.x), end);
+    } else {
+      philox_rows(a, b, tbegin, tensor, g, uu);
+    }
+#pragma unroll
+    for (int sl = 0; sl < 4; ++sl) {
+      const int k = 4 * g + sl;
+      const int64_t e = b + 4 * ((int64_t)k * kThreads + threadIdx.x);
+      if (!FULL && e >= end) continue;
+      const Divisor dv(norm[k], kFmtF32);
+      int32_t qq[4];
+      qsgd_quad(v[k], uu[sl], dv, a.levels, !(norm[k] != 0.0f), qq);
+      sink(k, e, qq);
+    }
+  }
+}
+
+constexpr int kBucketSumMax = 8;  // clients per launch; the calls chain groups (sum_group, omf_qsgd_dec.h)
+template <int N>
+struct BSumArgs {  // SumArgs of omf_qsgd_recv.hip; q[k] is client k's payload (levels, or the packed words),
+  const void* q[N];  // norm[k] its bucket-norm arena
+  const float* norm[N];
+  float* y;
+  float levels, inv_levels;
+  float divisor, pad_div;
+  int32_t init, fill;
+};
+
+// The plan's tables of bucket size 2^logd: boff on the device, nb on the host.  Built and uploaded at the
+// first call at that size (synchronous), kept for the plan's life (at most bucket::kSizes of them): no later
+// call allocates or synchronises.
+inline int bucket_tables(omf_plan* p, int logd, const int64_t** boff, int64_t* nb) {
+  const int i = logd - bucket::kMinLog2;
+  if (!p->d_boff[i]) {
+    std::vector<int64_t> h((size_t)p->nt);
+    const int64_t total = bucket::offsets(p->sizes.data(), p->nt, logd, h.data());
+    void* d = nullptr;
+    OMF_HIP(hipMalloc(&d, h.size() * sizeof(int64_t)));
+    if (const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice); e != hipSuccess) {
+      (void)hipFree(d);
+      return hip_fail(e, "hipMemcpy(boff)");
+    }
+    p->d_lazy.push_back(d);  // the plan owns it
+    p->d_boff[i] = static_cast<int64_t*>(d);
+    p->bucket_nb[i] = total;
+  }
+  *boff = p->d_boff[i];
+  *nb = p->bucket_nb[i];
+  return OMF_OK;
+}
+
+}  // namespace
 #endif  // __HIPCC__

@@ -48,70 +48,17 @@ namespace {
 
 // ---------------------------------------------------------------- encoder
 
-// Quantise V rows of the block at b against each row's own norm and store: quant_store (omf_qsgd_enc.h) with
-// a norm per row (the draws, the level math and the stores are its: philox_rows, qsgd_quad, store_quad).
-template <int WIDTH, bool HAS_U, bool FULL, int V>
-__device__ __forceinline__ void quant_store_rows(const float4 (&v)[V], const EncArgs& a, int64_t b, int64_t end,
-                                                 int64_t tbegin, int32_t tensor, const float (&norm)[V]) {
-  static_assert(V % 4 == 0, "rows come in groups of 4 (RNG slots)");
-#pragma unroll
-  for (int g = 0; g < V / 4; ++g) {
-    float4 uu[4];
-    if (HAS_U) {
-#pragma unroll
-      for (int sl = 0; sl < 4; ++sl)
-        uu[sl] = load_quad<FULL>(a.u, b + 4 * ((int64_t)(4 * g + sl) * kThreads + threadIdx.x), end);
-    } else {
-      philox_rows(a, b, tbegin, tensor, g, uu);
-    }
-#pragma unroll
-    for (int sl = 0; sl < 4; ++sl) {
-      const int k = 4 * g + sl;
-      const int64_t e = b + 4 * ((int64_t)k * kThreads + threadIdx.x);
-      if (!FULL && e >= end) continue;
-      const Divisor dv(norm[k], kFmtF32);
-      int32_t qq[4];
-      qsgd_quad(v[k], uu[sl], dv, a.levels, !(norm[k] != 0.0f), qq);
-      store_quad<WIDTH, FULL>(a, e, end, qq);
-    }
-  }
-}
-
-// One block [b, end) of V rows of tensor `tensor` (begins at tbegin; its norms at nbase of the bucket arena).
+// One block [b, end) of V rows of tensor `tensor` (begins at tbegin; its norms at nbase of the bucket arena):
+// bucket_front and quant_rows (omf_qsgd_bucket.h) with the int8 / int32 wire's store (store_quad).
 template <int WIDTH, bool HAS_U, bool FULL, int V>
 __device__ __forceinline__ void bucket_block(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int32_t tensor,
                                              int64_t nbase, int logd, float (*xch)[kWaves]) {
-  const int tid = (int)threadIdx.x;
   float4 v[V];
-  load_f4<V, FULL, true>(a.x, b, end, v);  // read once: non-temporal
-  scale_f4<V>(v, a);
-  const int64_t rel = (b - tbegin) + 4 * tid;  // this thread's row 0, from the tensor's begin
   float norm[V];
-  if (a.norm_in) {  // the caller's norms (uniform branch)
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const bool live = FULL || b + 4 * ((int64_t)k * kThreads + tid) < end;
-      norm[k] = live ? a.norm_in[nbase + ((rel + 1024 * k) >> logd)] : 0.0f;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) norm[k] = sq4(v[k], 0.0f);
-    bucket::bucket_sums<V>(norm, logd, xch);
-#pragma unroll
-    for (int k = 0; k < V; ++k) norm[k] = sqrtf(norm[k]);
-  }
-  // the bucket's first lane (of its first row) stores the norm
-  const int lane_mask = logd <= 10 ? (1 << (logd - 2)) - 1 : kThreads - 1;
-  const int row_mask = logd <= 10 ? 0 : (1 << (logd - 10)) - 1;
-  if ((tid & lane_mask) == 0) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if (k & row_mask) continue;
-      if (FULL || b + 4 * ((int64_t)k * kThreads + tid) < end) a.norm_out[nbase + ((rel + 1024 * k) >> logd)] = norm[k];
-    }
-  }
+  bucket_front<FULL, V>(a, b, end, tbegin, nbase, logd, xch, v, norm);
   if (!a.q) return;  // norms only (uniform)
-  quant_store_rows<WIDTH, HAS_U, FULL, V>(v, a, b, end, tbegin, tensor, norm);
+  quant_rows<HAS_U, FULL, V>(v, a, b, end, tbegin, tensor, norm,
+                             [&](int, int64_t e, const int32_t (&qq)[4]) { store_quad<WIDTH, FULL>(a, e, end, qq); });
 }
 
 // LOGD: log2 d at compile time (the butterfly's branches fold away), or 0: the kernel argument.
@@ -153,17 +100,6 @@ BucketKernel encode_kernel_static(int logd, bool w, bool u) {
 }
 
 // ---------------------------------------------------------------- decode and sum
-
-constexpr int kSumMax = 8;  // clients per launch; the call chains groups (sum_group, omf_qsgd_dec.h)
-template <int N>
-struct BSumArgs {  // SumArgs of omf_qsgd_recv.hip; norm[k] is client k's bucket-norm arena
-  const void* q[N];
-  const float* norm[N];
-  float* y;
-  float levels, inv_levels;
-  float divisor, pad_div;
-  int32_t init, fill;
-};
 
 template <int WIDTH, bool POW2>
 __device__ __forceinline__ void dec_quad(const int32_t* raw, float norm, float levels, float inv_levels, float (&yv)[4]) {
@@ -261,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_bucket_decode_sum(BSumArgs<N> a
 // An arena of fewer than 4 elements (one tensor at offset 0, one bucket): one thread per element, byte /
 // dword loads, `n` clients behind a uniform guard.
 template <int WIDTH, bool POW2>
-__global__ __launch_bounds__(64) void qsgd_bucket_sum_tiny(BSumArgs<kSumMax> a, int32_t n,
+__global__ __launch_bounds__(64) void qsgd_bucket_sum_tiny(BSumArgs<kBucketSumMax> a, int32_t n,
                                                            const int64_t* __restrict__ begins,
                                                            const int64_t* __restrict__ sizes,
                                                            const int64_t* __restrict__ boff, int32_t nt,
@@ -278,7 +214,7 @@ __global__ __launch_bounds__(64) void qsgd_bucket_sum_tiny(BSumArgs<kSumMax> a, 
   const int64_t ni = boff[t];  // i - begins[t] < 4 <= d: the tensor's first bucket
   float s = a.init ? a.y[i] : 0.0f;
 #pragma unroll
-  for (int c = 0; c < kSumMax; ++c) {
+  for (int c = 0; c < kBucketSumMax; ++c) {
     if (c < n) {
       const int32_t q = WIDTH == 1 ? (int32_t) reinterpret_cast<const int8_t*>(a.q[c])[i]
                                    : reinterpret_cast<const int32_t*>(a.q[c])[i];
@@ -290,42 +226,16 @@ __global__ __launch_bounds__(64) void qsgd_bucket_sum_tiny(BSumArgs<kSumMax> a, 
 
 // ---------------------------------------------------------------- host side
 
-constexpr const char* kMisaligned = "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)";
-constexpr const char* kBadSize = "bucket_size must be a power of two in [64, 4096]";
-
-// The plan's tables of bucket size 2^logd: boff on the device, nb on the host.  Built and uploaded at the
-// first call at that size (synchronous), kept for the plan's life (at most bucket::kSizes of them): no later
-// call allocates or synchronises.
-int bucket_tables(omf_plan* p, int logd, const int64_t** boff, int64_t* nb) {
-  const int i = logd - bucket::kMinLog2;
-  if (!p->d_boff[i]) {
-    std::vector<int64_t> h((size_t)p->nt);
-    const int64_t total = bucket::offsets(p->sizes.data(), p->nt, logd, h.data());
-    void* d = nullptr;
-    OMF_HIP(hipMalloc(&d, h.size() * sizeof(int64_t)));
-    if (const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice); e != hipSuccess) {
-      (void)hipFree(d);
-      return hip_fail(e, "hipMemcpy(boff)");
-    }
-    p->d_lazy.push_back(d);  // the plan owns it
-    p->d_boff[i] = static_cast<int64_t*>(d);
-    p->bucket_nb[i] = total;
-  }
-  *boff = p->d_boff[i];
-  *nb = p->bucket_nb[i];
-  return OMF_OK;
-}
-
 int encode_bucketed(omf_plan* p, const float* x, float alpha, int32_t s, int64_t d, const float* u, uint64_t seed,
                     uint64_t offset, const float* bnorm_in, void* q, float* bnorm_out, bool norm_only, void* stream) {
   if (!p) return fail(OMF_EINVAL, "plan is NULL");
   const int logd = bucket::log2_size(d);
-  if (logd < 0) return fail(OMF_EINVAL, kBadSize);
+  if (logd < 0) return fail(OMF_EINVAL, kBucketBadSize);
   if (s < 0 || s > 30) return fail(OMF_EINVAL, "bit_width must be in [0, 30] (levels = 2^bit_width is an int32 on the wire)");
   const int width = (1 << s) <= 127 ? 1 : 4;
   if (!x || !bnorm_out || (!norm_only && !q)) return fail(OMF_EINVAL, "x, q and bnorm_out must be non-NULL");
   if (!aligned(x, 16) || (u && !aligned(u, 16)) || (q && !aligned(q, width == 1 ? 4 : 16)))
-    return fail(OMF_EINVAL, kMisaligned);
+    return fail(OMF_EINVAL, kBucketMisaligned);
   if (!aligned(bnorm_out, 4) || (bnorm_in && !aligned(bnorm_in, 4))) return fail(OMF_EINVAL, "misaligned bucket norms");
   if (!p->d_block) return fail(OMF_EHIP, "the plan's tables are not on the device (an earlier upload failed)");
   DeviceGuard g(p->device);
@@ -369,13 +279,13 @@ void launch_sum(const BSumCall& c) {
   const omf_plan* p = c.p;
   const int n = c.g.n;
   if (p->arena_end < 4) {  // no whole quad: the element kernel
-    hipLaunchKernelGGL((qsgd_bucket_sum_tiny<W, P>), dim3(1), dim3(64), 0, c.st, sum_args<kSumMax>(c, n), n,
+    hipLaunchKernelGGL((qsgd_bucket_sum_tiny<W, P>), dim3(1), dim3(64), 0, c.st, sum_args<kBucketSumMax>(c, n), n,
                        (const int64_t*)p->d_begins, (const int64_t*)p->d_sizes, c.boff, p->nt, p->arena_end);
     return;
   }
   const int64_t qlast = (p->arena_end & ~(int64_t)3) - 4;  // the last whole quad of a payload
   const unsigned blocks = (unsigned)(p->n_dec_blocks * (kDecBlk / kSumBlk));
-  with_group_size<kSumMax>(n, [&](auto N) {
+  with_group_size<kBucketSumMax>(n, [&](auto N) {
     hipLaunchKernelGGL((qsgd_bucket_decode_sum<W, P, N()>), dim3(blocks), dim3(kThreads), 0, c.st, sum_args<N()>(c, N()),
                        (const uint32_t*)p->d_dec_binfo, (const int64_t*)p->d_begins, (const int64_t*)p->d_sizes, c.boff,
                        c.logd, p->nt, qlast, p->arena_end);
@@ -389,18 +299,18 @@ int sum_bucketed(omf_plan* p, const void* const* q, const float* const* bnorm, i
   const std::string who = plain ? "omf_qsgd_decode_bucketed" : "omf_qsgd_decode_sum_bucketed";
   if (!p) return fail(OMF_EINVAL, "plan is NULL");
   const int logd = bucket::log2_size(d);
-  if (logd < 0) return fail(OMF_EINVAL, kBadSize);
+  if (logd < 0) return fail(OMF_EINVAL, kBucketBadSize);
   if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
   if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
   if (nclients < 1) return fail(OMF_EINVAL, who + ": nclients must be >= 1");
   if (!q || !bnorm || !y) return fail(OMF_EINVAL, "q, bnorm and y_out must be non-NULL");
-  if (!aligned(y, 16)) return fail(OMF_EINVAL, kMisaligned);
+  if (!aligned(y, 16)) return fail(OMF_EINVAL, kBucketMisaligned);
   const int64_t nb = bucket::offsets(p->sizes.data(), p->nt, logd, nullptr);
   const size_t ybytes = (size_t)p->arena_end * 4;
   const size_t qbytes = width == 8 ? (size_t)((p->arena_end + 3) & ~(int64_t)3) : (size_t)p->arena_end * 4;
   for (int32_t k = 0; k < nclients; ++k) {
     if (!q[k] || !bnorm[k]) return fail(OMF_EINVAL, who + (plain ? ": q and bnorm must be non-NULL" : ": a NULL entry in q or bnorm"));
-    if (!aligned(q[k], width == 8 ? 4 : 16) || !aligned(bnorm[k], 4)) return fail(OMF_EINVAL, kMisaligned);
+    if (!aligned(q[k], width == 8 ? 4 : 16) || !aligned(bnorm[k], 4)) return fail(OMF_EINVAL, kBucketMisaligned);
     if (overlaps(y, ybytes, q[k], qbytes) || overlaps(y, ybytes, bnorm[k], (size_t)nb * 4))
       return fail(OMF_EINVAL, who + ": y_out overlaps a payload or norm buffer");
   }
@@ -412,8 +322,8 @@ int sum_bucketed(omf_plan* p, const void* const* q, const float* const* bnorm, i
   int64_t nb_table = 0;
   if (int r = bucket_tables(p, logd, &c.boff, &nb_table)) return r;
   c.p = p; c.y = y; c.st = (hipStream_t)stream; c.levels = lv.levels; c.inv_levels = lv.inv_levels; c.logd = logd;
-  for (int32_t k0 = 0; k0 < nclients; k0 += kSumMax) {
-    c.g = sum_group(nclients, kSumMax, init, divisor, k0);
+  for (int32_t k0 = 0; k0 < nclients; k0 += kBucketSumMax) {
+    c.g = sum_group(nclients, kBucketSumMax, init, divisor, k0);
     if (plain) c.g.fill = 0;
     c.q = q + k0; c.norm = bnorm + k0;
     if (width == 8) {

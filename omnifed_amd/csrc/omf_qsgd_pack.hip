@@ -23,32 +23,7 @@ using namespace omf;
 namespace {
 
 constexpr int64_t kTableBlk = omf::plan_layout::kDecBlk;  // elements per decoder-table block
-constexpr int kGroupBlk = 32 * kThreads;  // elements per workgroup of the pack and the decode
-static_assert(kGroupBlk == 2 * kTableBlk, "two table blocks per workgroup");
-
-// A thread's 32-element group: the whole workgroup inside one tensor (both table blocks marked
-// inside the same tensor), or the group's own tensor found from the block's first one (offsets
-// are multiples of 32: a group never spans two tensors).  Returns the elements of the group in
-// its tensor (0 = padding, the gap in front of the first tensor included, or past the arena) and
-// that tensor.
-__device__ __forceinline__ int group_tensor(const uint32_t* __restrict__ binfo, int64_t nbinfo,
-                                            const int64_t* __restrict__ begins, const int64_t* __restrict__ sizes,
-                                            int32_t nt, int64_t e0, bool* whole, int32_t* tensor) {
-  const int64_t k0 = 2 * (int64_t)blockIdx.x;
-  const uint32_t i0 = binfo[k0];
-  const uint32_t i1 = k0 + 1 < nbinfo ? binfo[k0 + 1] : 0u;
-  int32_t t = (int32_t)(i0 & 0x7fffffffu);  // the last tensor starting at or before the block
-  *whole = (i0 >> 31) && i1 == i0;
-  if (*whole) {
-    *tensor = t;
-    return 32;
-  }
-  while (t + 1 < nt && e0 >= begins[t + 1]) ++t;
-  *tensor = t;
-  if (e0 < begins[t]) return 0;  // padding before the first tensor
-  const int64_t lim = min((int64_t)32, begins[t] + sizes[t] - e0);
-  return lim > 0 ? (int)lim : 0;
-}
+static_assert(kGroupBlk == 2 * kTableBlk, "two table blocks per workgroup (group_tensor, omf_qsgd_dec.h)");
 
 // Pack over the arena, one workgroup per 8 Ki-element block: each thread packs its 32-element
 // group into b words.  The payload loads are issued before the block's table entry arrives,
@@ -101,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_pack(const void* __restrict__ q
   int nb = 0, w = 0;
 #pragma unroll
   for (int i = 0; i < 32; ++i) {
-    acc |= (uint64_t)((uint32_t)lv[i] + (uint32_t)L) << nb;  // modulo 2^32: q + L passes INT32_MAX from L = 2^30 on
+    acc |= (uint64_t)qsgd_code(lv[i], L) << nb;
     nb += b;
     if (nb >= 32) {
       if (B) wd[w++] = (uint32_t)acc;  // static index once unrolled
@@ -167,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
       acc |= (uint64_t)wd[w++] << nb;
       nb += 32;
     }
-    const int32_t qi = (int32_t)((uint32_t)(acc & mask) - (uint32_t)L);  // modulo 2^32 (b = 32: codes above INT32_MAX)
+    const int32_t qi = qsgd_level((uint32_t)(acc & mask), L);
     acc >>= b;
     nb -= b;
     tile[threadIdx.x * 33 + i] = qsgd_dec_elem<POW2>(nrm, qi, levels, inv_levels);
@@ -196,22 +171,9 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_packed(const uint32_t* _
 }
 
 // N clients' packed payloads decoded and summed in one pass (omf_qsgd_decode_sum_packed), in
-// qsgd_decode_packed's shape: one workgroup per 8 Ki-element block, one 32-element group per thread.
-//   s = init ? y : +0;  s = fl32(s + qsgd_dec_elem(norm_c[t], code_c - L))  c = 0..N-1;
-//   y = divisor != 0 ? s / divisor : s
-// the bytes of omf_qsgd_decode_sum on the same levels unpacked.  All N clients' b words of the
-// thread's group go out first (unconditional, clamped to the packed arena's last group), with the
-// block's table entry and the N norms in flight; the 32 running sums stay in registers, added in
-// client order.  With `init` the sums start from y, which is read as lane-contiguous 16-byte loads
-// and brought into group order through the 33-word-row tile (fp32 addition does not let y be added
-// last); the sums leave through the same tile as lane-contiguous non-temporal 16-byte stores.
-// The client pointers are kernel arguments indexed at compile time (N is a template parameter: a
-// runtime index into a by-value array is copied to scratch).  A block not inside one tensor finds
-// each group's tensor and goes element by element where a tensor ends inside a quad; with `fill`
-// it also writes the padding of [0, arena_end) (fl32(+0 / pad_div), or +0), otherwise padding is
-// neither read nor written.
-// B: compile-time code width (2..10), or 0 = the runtime width b_rt, whose codes are read from
-// memory element by element (a register array indexed by a runtime word count goes to scratch).
+// qsgd_decode_packed's shape: one workgroup per 8 Ki-element block, one 32-element group per thread, with a
+// norm per tensor; the bytes of omf_qsgd_decode_sum on the same levels unpacked.  The block's body, and the
+// meaning of B, is packed_sum_block (omf_qsgd_dec.h), shared with the bucketed packed wire.
 constexpr int kPackedSumMax = 8;     // clients per launch; omf_qsgd_decode_sum_packed chains groups
 constexpr int kPackedSumMaxWide = 4; // the same for the runtime-width instance (32 * N unrolled two-word reads)
 template <int N>
@@ -235,136 +197,12 @@ __global__ __launch_bounds__(kThreads) void qsgd_decode_sum_packed(PackedSumArgs
                                                                    const int64_t* __restrict__ begins,
                                                                    const int64_t* __restrict__ sizes, int32_t nt,
                                                                    int64_t arena_end) {
-  constexpr int G = kGroupBlk;
   __shared__ float tile[kThreads * 33];
   __shared__ int32_t s_lim[kThreads];
-  const int b = B ? B : a.b_rt;
-  const int64_t base = (int64_t)blockIdx.x * G;
-  const int64_t e0 = base + 32 * (int64_t)threadIdx.x;
-  // unconditional loads, clamped to the packed arena's last group
-  const int64_t woff = min(e0 >> 5, (arena_end - 1) >> 5) * (int64_t)b;
-  uint32_t wd[N][B ? B : 1];
-  if (B) {
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-#pragma unroll
-      for (int i = 0; i < (B ? B : 1); ++i) wd[c][i] = __builtin_nontemporal_load(a.packed[c] + woff + i);
-    }
-  }
-  bool whole;  // uniform: from the block's two table entries
-  int32_t t;
-  const int lim = group_tensor(binfo, nbinfo, begins, sizes, nt, e0, &whole, &t);
-  if (!whole) {
-    s_lim[threadIdx.x] = lim;
-    __syncthreads();
-  }
-  float nrm[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) nrm[c] = lim > 0 ? a.norm[c][t] : 0.0f;
-  float s[32];
-  if (a.init) {  // uniform
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-      const int e = 4 * (v * kThreads + (int)threadIdx.x);  // element of this block
-      const int l = whole ? 4 : s_lim[e >> 5] - (e & 31);   // elements of the quad inside a tensor
-      const float* yi = a.y + base + e;
-      f32x4_t pv = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (l >= 4) {
-        pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(yi));
-      } else {
-        if (l > 0) pv[0] = yi[0];
-        if (l > 1) pv[1] = yi[1];
-        if (l > 2) pv[2] = yi[2];
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) tile[((e + c) >> 5) * 33 + ((e + c) & 31)] = pv[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 32; ++i) s[i] = tile[threadIdx.x * 33 + i];  // this thread's row: rewritten by it alone below
-  } else {
-#pragma unroll
-    for (int i = 0; i < 32; ++i) s[i] = 0.0f;
-  }
-  const uint64_t mask = (1ull << b) - 1ull;
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    uint64_t acc = 0;
-    int nb = 0, w = 0;
-    const uint32_t* p = a.packed[c] + woff;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      uint32_t code;
-      if (B) {
-        if (nb < b) {
-          acc |= (uint64_t)wd[c][w++] << nb;
-          nb += 32;
-        }
-        code = (uint32_t)(acc & mask);
-        acc >>= b;
-        nb -= b;
-      } else {  // bits [i b, (i + 1) b) of the group's b words: at most two words, both inside the group
-        const int bit = i * b, wi = bit >> 5;
-        const uint64_t two = ((uint64_t)p[min(wi + 1, b - 1)] << 32) | p[wi];
-        code = (uint32_t)((two >> (bit & 31)) & mask);
-      }
-      const int32_t qi = (int32_t)(code - (uint32_t)a.L);
-      s[i] = __fadd_rn(s[i], qsgd_dec_elem<POW2>(nrm[c], qi, a.levels, a.inv_levels));
-    }
-    // One client at a time: the sums are pinned in their registers here.  Left free, the compiler sinks
-    // every client's unpack and adds to the end and holds all their codes at once (256 VGPRs, one
-    // wave per SIMD at N = 8).
-#pragma unroll
-    for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(s[i]));
-  }
-  if (a.divisor != 0.0f) {
-#pragma unroll
-    for (int i = 0; i < 32; ++i) s[i] = s[i] / a.divisor;
-  }
-#pragma unroll
-  for (int i = 0; i < 32; ++i) tile[threadIdx.x * 33 + i] = s[i];
-  __syncthreads();
-  const float pad = a.pad_div != 0.0f ? 0.0f / a.pad_div : 0.0f;
-#pragma unroll
-  for (int v = 0; v < 8; ++v) {
-    const int e = 4 * (v * kThreads + (int)threadIdx.x);
-    float f[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) f[c] = tile[((e + c) >> 5) * 33 + ((e + c) & 31)];
-    float* yo = a.y + base + e;
-    const int l = whole ? 4 : s_lim[e >> 5] - (e & 31);
-    if (l >= 4) {
-      store_nt(yo, make_float4(f[0], f[1], f[2], f[3]));
-    } else if (a.fill && base + e + 4 <= arena_end) {  // a quad with padding, all of it inside the arena
-      store_nt(yo, make_float4(l > 0 ? f[0] : pad, l > 1 ? f[1] : pad, l > 2 ? f[2] : pad, pad));
-    } else {
-      for (int c = 0; c < 4; ++c) {
-        if (c < l) yo[c] = f[c];
-        else if (a.fill && base + e + c < arena_end) yo[c] = pad;
-      }
-    }
-  }
-}
-
-// The plan's arena as the pack and the decode walk it.
-struct ArenaArgs {
-  const uint32_t* binfo;
-  int64_t nbinfo;
-  const int64_t* begins;
-  const int64_t* sizes;
-  int32_t nt;
-  int64_t arena_end;
-};
-
-// f(std::integral_constant<int, B>): B = b for the compile-time code widths 2..10, else 0 (the runtime width).
-template <class F>
-void with_code_bits(int b, F&& f) {
-  switch (b) {
-#define OMF_B(B) case B: f(std::integral_constant<int, B>{}); break;
-    OMF_B(2) OMF_B(3) OMF_B(4) OMF_B(5) OMF_B(6) OMF_B(7) OMF_B(8) OMF_B(9) OMF_B(10)
-#undef OMF_B
-    default: f(std::integral_constant<int, 0>{}); break;
-  }
+  packed_sum_block<B, POW2, N>(
+      a, a.L, a.b_rt, [&](int c) { return a.packed[c]; },
+      [&](int c, int lim, int32_t t, int64_t) { return lim > 0 ? a.norm[c][t] : 0.0f; }, binfo, nbinfo, begins, sizes, nt,
+      arena_end, tile, s_lim);
 }
 
 template <int WIDTH>
@@ -407,21 +245,6 @@ void dispatch_psum(const PackedSumCall& c, int n) {
   with_code_bits(c.b, [&](auto B) {
     with_group_size<(B() != 0 ? kPackedSumMax : kPackedSumMaxWide)>(n, [&](auto N) { launch_psum_n<B(), P, N()>(c); });
   });
-}
-
-// The plan's arena for the packed wire, or an error: every tensor offset a multiple of 32
-// elements (a tensor's stream then starts on a word, and a 32-element group lies in one tensor).
-int packed_arena(const omf_plan* plan, ArenaArgs* a, dim3* grid) {
-  for (const int64_t o : plan->offsets)
-    if (o & 31) return fail(OMF_EINVAL, "the packed wire needs tensor offsets that are multiples of 32 elements");
-  a->binfo = plan->d_dec_binfo;
-  a->nbinfo = plan->n_dec_blocks;
-  a->begins = plan->d_begins;
-  a->sizes = plan->d_sizes;
-  a->nt = plan->nt;
-  a->arena_end = plan->arena_end;
-  *grid = dim3((unsigned)((a->arena_end + kGroupBlk - 1) / kGroupBlk));
-  return OMF_OK;
 }
 
 }  // namespace

@@ -36,6 +36,7 @@ import torch
 from . import global_grpc_pb2
 from ..compression.qsgd import (
     QSGD_BUCKETED_COMPRESSION_NAME,
+    QSGD_BUCKETED_PACKED_COMPRESSION_NAME,
     QSGD_COMPRESSION_NAME,
     QSGD_PACKED_COMPRESSION_NAME,
     QSGDQuantCompression,
@@ -51,7 +52,11 @@ GlobalHybridCompressor = Union[TopKCompression, QSGDQuantCompression]
 
 _QSGD_NUMPY_DTYPES = {8: np.int8, 32: np.int32}
 _QSGD_TORCH_DTYPES = {8: torch.int8, 32: torch.int32}
-_QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME)
+_QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME,
+               QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+# the wires whose values_data is a stream of b-bit codes / whose meta_tensor holds bucket norms
+_QSGD_CODE_TYPES = (QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+_QSGD_BUCKET_TYPES = (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
 _TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
 # the two types that share the packed index wire: a message or an update may mix them
 _TOPK_PACKED_TYPES = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
@@ -92,7 +97,8 @@ def compression_mode_name(compressor: Optional[GlobalHybridCompressor]) -> str:
 
 def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_ratio: float = 0.01,
                             bit_width: int = 8, device="cpu", packed_wire: bool = False,
-                            value_bits=None, bucket_size=None) -> Optional[GlobalHybridCompressor]:
+                            value_bits=None, bucket_size=None,
+                            bucket_packed: bool = False) -> Optional[GlobalHybridCompressor]:
     """global_grpc_compression.py:35-52.  ``packed_wire`` (default off): the scheme's opt-in bit-packed
     wire — ``QSGDBitPackedCompression`` (the levels in ceil(log2(2L + 1)) bits) or
     ``TopKBitPackedCompression`` (the indices in max(1, bit_length(n - 1)) bits); neither is readable
@@ -101,10 +107,15 @@ def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_rat
     max |v| in value_bits + 2 bits each, the quantisation error fed back through the residual.
     ``bucket_size`` (default None; needs ``scheme="qsgd"`` and no ``packed_wire``): ``QSGDBucketedCompression``
     layers, every bucket of that many consecutive elements (a power of two in [64, 4096]) quantised against
-    its own norm; fp32 tensors only."""
+    its own norm; fp32 tensors only.  ``bucket_packed`` (default off; needs ``bucket_size``):
+    ``QSGDBucketedPackedCompression`` layers, the bucketed update's codes on the bit-packed wire, packed inside
+    the encode pass."""
     if not enabled:
         return None
     scheme_norm = str(scheme).lower()
+    if bucket_packed and (scheme_norm != "qsgd" or bucket_size is None):
+        raise ValueError(f"bucket_packed requires scheme='qsgd' and a bucket_size (got scheme={scheme!r}, "
+                         f"bucket_size={bucket_size!r})")
     if bucket_size is not None and scheme_norm != "qsgd":
         raise ValueError(f"bucket_size requires scheme='qsgd' (got scheme={scheme!r})")
     if value_bits is not None and scheme_norm != "topk":
@@ -114,7 +125,7 @@ def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_rat
                                value_bits=value_bits)
     if scheme_norm == "qsgd":
         return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire),
-                                    bucket_size=bucket_size)
+                                    bucket_size=bucket_size, bucket_packed=bool(bucket_packed))
     raise ValueError(f"Unsupported global_compression.scheme={scheme!r}; expected 'topk' or 'qsgd'")
 
 
@@ -151,8 +162,10 @@ def hybrid_global_compressor_from_cfg(cfg, device="cpu") -> Optional[GlobalHybri
     packed = bool(_select(cfg, "engine.hybrid.global_compression.packed_wire", False))  # opt-in, ours
     value_bits = _select(cfg, "engine.hybrid.global_compression.value_bits", None)  # opt-in, ours
     bucket_size = _select(cfg, "engine.hybrid.global_compression.bucket_size", None)  # opt-in, ours
+    bucket_packed = bool(_select(cfg, "engine.hybrid.global_compression.bucket_packed", False))  # opt-in, ours
     return build_global_compressor(enabled=enabled, scheme=scheme, compress_ratio=ratio, bit_width=bit_width,
-                                   device=device, packed_wire=packed, value_bits=value_bits, bucket_size=bucket_size)
+                                   device=device, packed_wire=packed, value_bits=value_bits, bucket_size=bucket_size,
+                                   bucket_packed=bucket_packed)
 
 
 # ---------------------------------------------------------------- layer builders (host)
@@ -202,6 +215,16 @@ def qsgd_bucketed_layer_from_payload(name: str, shape, payload: bytes, bnorms, w
     tensor's ceil(n / d) fp32 bucket norms (little-endian), and d in ``param_shape``."""
     layer = qsgd_layer_from_payload(name, shape, payload, 0.0, width, levels)
     layer.compression_type = QSGD_BUCKETED_COMPRESSION_NAME
+    layer.meta_tensor = np.ascontiguousarray(bnorms, dtype="<f4").tobytes()
+    layer.param_shape.append(int(bucket_size))
+    return layer
+
+
+def qsgd_bucketed_packed_layer_from_payload(name: str, shape, packed: bytes, bnorms, levels: int, bucket_size: int):
+    """The opt-in bucketed QSGD ``LayerState`` on the bit-packed wire: the packed layer's values (the tensor's
+    ceil(n b / 8) stream bytes), width = b and ``values_dtype``; the bucketed layer's norms and d."""
+    layer = qsgd_packed_layer_from_payload(name, shape, packed, 0.0, levels)
+    layer.compression_type = QSGD_BUCKETED_PACKED_COMPRESSION_NAME
     layer.meta_tensor = np.ascontiguousarray(bnorms, dtype="<f4").tobytes()
     layer.param_shape.append(int(bucket_size))
     return layer
@@ -450,7 +473,7 @@ def _decode_topk_layer(layer, *, base_tensor: Optional[torch.Tensor] = None, dev
 
 def _payload_nbytes(layer) -> int:
     n = int(np.prod(tuple(layer.original_shape)))
-    if layer.compression_type == QSGD_PACKED_COMPRESSION_NAME:
+    if layer.compression_type in _QSGD_CODE_TYPES:
         return (n * layer.width + 7) // 8
     return n * (layer.width // 8)
 
@@ -461,7 +484,7 @@ def _check_qsgd_payload(layer, payload: bytes) -> None:
     if not payload:
         raise ValueError(f"QSGD layer {layer.layer_name!r} missing values_data")
     if len(payload) != _payload_nbytes(layer):
-        kind = "packed QSGD" if layer.compression_type == QSGD_PACKED_COMPRESSION_NAME else "QSGD"
+        kind = "packed QSGD" if layer.compression_type in _QSGD_CODE_TYPES else "QSGD"
         raise ValueError(f"cannot reshape {kind} payload of {len(payload)} bytes into {tuple(layer.original_shape)}")
 
 
@@ -494,7 +517,8 @@ def _check_packed_fields(layer):
 
 
 def _check_bucketed_fields(layer):
-    """The bucketed layer's fields: the bucket size, one norm per bucket, the plain layer's width and level."""
+    """The bucketed layer's fields: the bucket size, one norm per bucket, the plain layer's width and level — or,
+    on the bit-packed wire, the packed layer's (width = packed_bits(level))."""
     d = int(layer.param_shape[0]) if len(layer.param_shape) == 1 else 0
     if d not in codec.BUCKET_SIZES:
         _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported bucket size {list(layer.param_shape)}")
@@ -502,10 +526,11 @@ def _check_bucketed_fields(layer):
     if not layer.meta_tensor or len(layer.meta_tensor) != 4 * nb:
         _field_error(layer, f"QSGD layer {layer.layer_name!r}: meta_tensor of {len(layer.meta_tensor)} bytes, "
                             f"expected {4 * nb} ({nb} bucket norms)")
-    if layer.width not in _QSGD_NUMPY_DTYPES:
-        _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported width={layer.width}")
     if layer.level <= 0:
         _field_error(layer, f"QSGD layer {layer.layer_name!r} has invalid level={layer.level}")
+    packed = layer.compression_type == QSGD_BUCKETED_PACKED_COMPRESSION_NAME
+    if layer.width != codec.packed_bits(layer.level) if packed else layer.width not in _QSGD_NUMPY_DTYPES:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported width={layer.width}")
 
 
 def _check_qsgd_layer(layer, payload: bytes):
@@ -520,7 +545,7 @@ def _check_packed_layer(layer, payload: bytes):
 
 def _decode_qsgd_layer(layer, *, device=None) -> torch.Tensor:
     """global_grpc_compression.py:163-182, decoded on the GPU."""
-    if layer.compression_type in (QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME):
+    if layer.compression_type in (QSGD_PACKED_COMPRESSION_NAME, *_QSGD_BUCKET_TYPES):
         if layer.compression_type == QSGD_PACKED_COMPRESSION_NAME:
             _check_packed_layer(layer, layer.values_data)
         else:
@@ -582,7 +607,7 @@ def wire_size(layers) -> Dict[str, int]:
             payload += len(L.values_data) + len(L.indices_data) + 4 * len(L.param_update)
             if L.compression_type == TOPK_QUANT_COMPRESSION_NAME:
                 payload += len(L.meta_tensor)  # the scale
-        if L.compression_type == QSGD_BUCKETED_COMPRESSION_NAME:
+        if L.compression_type in _QSGD_BUCKET_TYPES:
             payload += len(L.meta_tensor)  # the bucket norms
         shape = tuple(L.original_shape) or tuple(L.param_shape)
         dense += 4 * int(np.prod(shape)) if shape else 0
@@ -745,9 +770,11 @@ def qsgd_layers_from_arena(plan, q: torch.Tensor, norms: torch.Tensor, names, sh
 
 
 def qsgd_bucketed_layers_from_arena(plan, q: torch.Tensor, bnorms: torch.Tensor, names, shapes, levels: int,
-                                    bucket_size: int, stream=None) -> list:
+                                    bucket_size: int, stream=None, packed: bool = False) -> list:
     """``qsgd_layers_from_arena`` for a bucketed encode: the bucket-norm arena copied first, then the payload
-    arena in chunks.  A tensor whose bucket norms are all zero gets ``None`` (the dense passthrough)."""
+    arena in chunks.  A tensor whose bucket norms are all zero gets ``None`` (the dense passthrough).
+    ``packed``: ``q`` is the packed arena of ``qsgd_encode_bucketed_packed`` (tensor t's stream at byte
+    ``offsets[t] * b / 8``), the layers ``QSGDBucketedPackedCompression`` ones."""
     stream = torch.cuda.current_stream(plan.device) if stream is None else stream
     width, _ = choose_qsgd_storage_width(levels)
     boff, nb = plan.bucket_layout(bucket_size)
@@ -760,11 +787,18 @@ def qsgd_bucketed_layers_from_arena(plan, q: torch.Tensor, bnorms: torch.Tensor,
         ev.synchronize()
         host = nh[:nb].numpy().copy()
     mine = [host[b0:b1] for b0, b1 in zip(boff, boff[1:] + [nb])]
-    isz = q.element_size()
-    spans = [(o * isz, n * isz if m.any() else 0) for o, n, m in zip(plan.offsets, plan.sizes, mine)]
+    if packed:
+        b = codec.packed_bits(levels)
+        spans = [(o * b // 8, (n * b + 7) // 8 if m.any() else 0) for o, n, m in zip(plan.offsets, plan.sizes, mine)]
+    else:
+        isz = q.element_size()
+        spans = [(o * isz, n * isz if m.any() else 0) for o, n, m in zip(plan.offsets, plan.sizes, mine)]
     layers: List = [None] * plan.nt
     for k, payload in hostio.device_to_bytes(q, spans, stream=stream):
-        layers[k] = qsgd_bucketed_layer_from_payload(names[k], shapes[k], payload, mine[k], width, levels, bucket_size)
+        if packed:
+            layers[k] = qsgd_bucketed_packed_layer_from_payload(names[k], shapes[k], payload, mine[k], levels, bucket_size)
+        else:
+            layers[k] = qsgd_bucketed_layer_from_payload(names[k], shapes[k], payload, mine[k], width, levels, bucket_size)
     return layers
 
 
@@ -786,10 +820,11 @@ def _encode_updates(updates, compressor, weight) -> list:
         levels = 2**compressor.s
         if compressor.bucket_size is not None:  # one launch, one norm per bucket
             plan, q, bn = encode_bucketed(flats, compressor.s, compressor.bucket_size, dev, compressor._next_call(),
-                                          alpha=_alpha(weight), key=compressor.philox_key())
+                                          alpha=_alpha(weight), key=compressor.philox_key(),
+                                          packed=compressor.bucket_packed)
             got = qsgd_bucketed_layers_from_arena(plan, q, bn, [names[i] for i in comp_idx],
                                                   [tuple(updates[names[i]].shape) for i in comp_idx], levels,
-                                                  compressor.bucket_size)
+                                                  compressor.bucket_size, packed=compressor.bucket_packed)
             groups = []
             for i, L in zip(comp_idx, got):
                 layers[i] = L
@@ -822,9 +857,15 @@ def _decode_qsgd_batch(layers, dev: torch.device, host: bool = False):
     width, level = layers[0].width, layers[0].level
     sizes = [max(int(np.prod(tuple(L.original_shape))), 1) for L in layers]
     plan = codec.Plan.get(sizes, device=dev)
-    if layers[0].compression_type == QSGD_BUCKETED_COMPRESSION_NAME:  # the layers share d (_scan_layers)
+    if layers[0].compression_type in _QSGD_BUCKET_TYPES:  # the layers share d (_scan_layers)
         d = int(layers[0].param_shape[0])
         bn = np.concatenate([np.frombuffer(L.meta_tensor, dtype="<f4") for L in layers]).astype(np.float32)
+        if layers[0].compression_type == QSGD_BUCKETED_PACKED_COMPRESSION_NAME:  # tensor t at byte offsets[t] * b / 8
+            words = plan.packed_words(level)
+            qd = torch.empty(words, dtype=torch.int32, device=dev)
+            items = [(o * width // 8, (lambda L=L: L.values_data)) for L, o in zip(layers, plan.offsets)]
+            hostio.bytes_to_device(items, qd, 4 * words, check=lambda i, p: _check_qsgd_payload(layers[i], p))
+            return plan.qsgd_decode_bucketed_packed(qd, level, d, torch.from_numpy(bn).to(dev)), plan
         isz = width // 8
         qd = torch.empty(plan.payload_elems(width), dtype=_QSGD_TORCH_DTYPES[width], device=dev)
         items = [(o * isz, (lambda L=L: L.values_data)) for L, o in zip(layers, plan.offsets)]
@@ -1018,7 +1059,7 @@ def _validate_layer(layer):
         _check_qsgd_fields(layer)  # the payload's size: checked as it is staged (_decode_qsgd_batch)
     elif ct == QSGD_PACKED_COMPRESSION_NAME:
         _check_packed_fields(layer)
-    elif ct == QSGD_BUCKETED_COMPRESSION_NAME:
+    elif ct in _QSGD_BUCKET_TYPES:
         _check_bucketed_fields(layer)
         _check_qsgd_payload(layer, layer.values_data)  # here too (one more copy of the payload), and as it is staged
     else:
@@ -1036,7 +1077,7 @@ def _scan_layers(proto_layers):
         got = _validate_layer(L)
         if got is not None:
             topk.append((L, *got))
-        elif L.compression_type == QSGD_BUCKETED_COMPRESSION_NAME:
+        elif L.compression_type in _QSGD_BUCKET_TYPES:
             groups.setdefault((L.compression_type, L.width, L.level, int(L.param_shape[0])), []).append(L)
         elif L.compression_type in _QSGD_TYPES:
             groups.setdefault((L.compression_type, L.width, L.level), []).append(L)

@@ -47,6 +47,10 @@ QSGD_PACKED_COMPRESSION_NAME = "QSGDBitPackedCompression"
 # bucket of d consecutive elements quantised against its own norm (include/omf_codec.h
 # omf_qsgd_encode_bucketed); meta_tensor holds the tensor's ceil(n / d) norms, param_shape = [d].
 QSGD_BUCKETED_COMPRESSION_NAME = "QSGDBucketedCompression"
+# Opt-in bucket norms on the bit-packed wire (not reference-compatible): the bucketed layer's norms and
+# param_shape = [d], the packed layer's codes, width = packed_bits(level) and values_dtype "packed.u{b}"
+# (include/omf_codec.h omf_qsgd_encode_bucketed_packed: the codes leave the encode pass already packed).
+QSGD_BUCKETED_PACKED_COMPRESSION_NAME = "QSGDBucketedPackedCompression"
 
 
 def should_compress_tensor(x: torch.Tensor) -> bool:
@@ -97,17 +101,18 @@ def _arena(flats: Sequence[torch.Tensor], dev: torch.device, plan) -> torch.Tens
 
 
 def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: int, dev: torch.device,
-                    call_index: int = 0, alpha: float = 1.0, key: int = 0):
+                    call_index: int = 0, alpha: float = 1.0, key: int = 0, packed: bool = False):
     """Encode flat fp32 tensors with bucket norms in ONE launch (``Plan.qsgd_encode_bucketed``, on-device
     draws): ``(plan, q_arena, bnorms_dev)``, tensor k's norms at ``plan.bucket_layout(bucket_size)[0][k]``.
+    ``packed``: ``Plan.qsgd_encode_bucketed_packed``, ``q_arena`` the packed arena (``qsgd_pack``'s layout).
     A bf16 / fp16 tensor raises ``ValueError`` (fp32 arenas only)."""
     for f in flats:
         if f.dtype != torch.float32:
             raise ValueError(f"bucketed QSGD encodes float32 tensors, not {f.dtype}")
     plan = codec.Plan.get([int(f.numel()) for f in flats], device=dev)
     x = gather_arena(flats, dev, plan)
-    q, bn = plan.qsgd_encode_bucketed(x, int(bit_width), bucket_size, alpha=alpha, seed=int(key) & (2**64 - 1),
-                                      offset=call_index)
+    encode = plan.qsgd_encode_bucketed_packed if packed else plan.qsgd_encode_bucketed
+    q, bn = encode(x, int(bit_width), bucket_size, alpha=alpha, seed=int(key) & (2**64 - 1), offset=call_index)
     return plan, q, bn
 
 
@@ -213,7 +218,7 @@ class QSGDQuantCompression(Compression):
     """QSGD (Alistarh et al., 2017), Algorithm 1 — on the GPU."""
 
     def __init__(self, bit_width: int = 8, device="cpu", rng: str = "philox", packed_wire: bool = False,
-                 bucket_size: Optional[int] = None):
+                 bucket_size: Optional[int] = None, bucket_packed: bool = False):
         super().__init__()
         self.s = int(bit_width)
         self.packed_wire = bool(packed_wire)  # encode_updates_dict / encode_layer_state emit packed layers
@@ -226,9 +231,14 @@ class QSGDQuantCompression(Compression):
         if self.bucket_size is not None:
             codec.bucket_layout([], self.bucket_size)  # ValueError for a size that is not allowed
             if self.packed_wire:
-                raise ValueError("bucket_size and packed_wire=True cannot be combined (no packed bucketed wire)")
+                raise ValueError("bucket_size and packed_wire=True cannot be combined (bucket_packed=True asks for "
+                                 "the packed bucketed wire)")
             if rng == "mt19937":
                 raise ValueError("bucket_size and rng='mt19937' cannot be combined (the reference has no buckets)")
+        # opt-in: the bucketed update's codes on the bit-packed wire (QSGDBucketedPackedCompression layers)
+        self.bucket_packed = bool(bucket_packed)
+        if self.bucket_packed and self.bucket_size is None:
+            raise ValueError("bucket_packed=True requires bucket_size")
         self.rng = rng
         self._calls = 0
         self._instance = next(_INSTANCES)

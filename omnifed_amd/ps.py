@@ -176,12 +176,14 @@ class DeviceAggregator:
         packed arena (``qsgd_pack``'s layout, tensor t at byte ``offsets[t] * b / 8``) and ``width`` the
         code's bits; an update's QSGD layers are all packed or all plain.  ``QSGDBucketedCompression`` layers
         (one bucket size per update, never mixed with the other two) give ``packed = ("bucket", d)`` and
-        ``norms`` the plan's bucket-norm arena."""
+        ``norms`` the plan's bucket-norm arena; ``QSGDBucketedPackedCompression`` layers (likewise)
+        ``packed = ("bucket_packed", d)``, ``payload`` the packed arena and ``width`` the code's bits."""
         from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
                                                                   _validate_layer, check_topk_indices, stage_topk)
         from .hybrid.communicator.global_grpc_compression import QuantValues
-        from .hybrid.compression import (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME,
-                                         TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
+        from .hybrid.compression import (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME,
+                                         QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME,
+                                         TOPK_QUANT_COMPRESSION_NAME)
 
         last: Dict[str, object] = {}
         topk_payload: Dict[str, tuple] = {}
@@ -194,10 +196,12 @@ class DeviceAggregator:
                 topk_payload[L.layer_name] = got
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
         packed_topk = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
-        qsgd_types = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME)
-        known = (*qsgd_types, "TopKCompression", *packed_topk, "")
+        qsgd_types = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME,
+                      QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+        topk_types = ("TopKCompression", *packed_topk)
+        known = (*qsgd_types, *topk_types, "")
         qsgd = [L for L in kept if L.compression_type in qsgd_types]
-        topk = [L for L in kept if L.compression_type in known[3:6]]
+        topk = [L for L in kept if L.compression_type in topk_types]
         dense = [L for L in kept if L.compression_type == ""]
         if any(L.compression_type not in known for L in kept):
             bad = next(L for L in kept if L.compression_type not in known)
@@ -209,10 +213,12 @@ class DeviceAggregator:
             packed = qsgd[0].compression_type == QSGD_PACKED_COMPRESSION_NAME  # width: the code's bits
             if qsgd[0].compression_type == QSGD_BUCKETED_COMPRESSION_NAME:  # the wire's marker: ("bucket", d)
                 packed = ("bucket", int(qsgd[0].param_shape[0]))
+            if qsgd[0].compression_type == QSGD_BUCKETED_PACKED_COMPRESSION_NAME:
+                packed = ("bucket_packed", int(qsgd[0].param_shape[0]))
             if any(L.compression_type != qsgd[0].compression_type
                    or (isinstance(packed, tuple) and int(L.param_shape[0]) != packed[1]) for L in qsgd):
-                raise ValueError("mixed QSGD width/level within one update (one wire per update: plain, bit-packed "
-                                 "or bucketed of one bucket size)")
+                raise ValueError("mixed QSGD width/level within one update (one wire per update: plain, bit-packed, "
+                                 "bucketed or packed bucketed of one bucket size)")
             if any(L.width != width or L.level != level for L in qsgd):
                 raise ValueError("mixed QSGD width/level within one update")
             bucketed = isinstance(packed, tuple)
@@ -232,7 +238,7 @@ class DeviceAggregator:
                 # plain: tensor t at byte offsets[t] * width / 8; packed: at offsets[t] * b / 8 (qsgd_pack's arena)
                 items.append((self.plan.offsets[i] * width // 8, (lambda L=L: L.values_data)))
 
-            if packed is True:
+            if packed is True or (bucketed and packed[0] == "bucket_packed"):  # a packed arena of b-bit codes
                 def check(k, payload):
                     _check_qsgd_payload(qsgd[k], payload)  # against the layer's own shape
                     n = self.plan.sizes[self.index[qsgd[k].layer_name]]
@@ -312,6 +318,8 @@ class DeviceAggregator:
             qd, width, level, nd, packed = q_args
             if packed is True:
                 self.plan.qsgd_decode_packed(qd, level, nd, y_out=self.acc, accumulate=True)
+            elif packed and packed[0] == "bucket_packed":
+                self.plan.qsgd_decode_bucketed_packed(qd, level, packed[1], nd, y_out=self.acc, accumulate=True)
             elif packed:  # ("bucket", d)
                 self.plan.qsgd_decode_bucketed(qd, width, level, packed[1], nd, y_out=self.acc, accumulate=True)
             else:
@@ -333,7 +341,8 @@ class DeviceAggregator:
         the per-update decode at every run length measured).  Updates on the packed wire
         form runs of their own, by level, applied by ONE ``qsgd_decode_sum_packed(init=True)`` (measured
         the same way), bucketed updates runs by ``(width, level, bucket size)`` applied by ONE
-        ``qsgd_decode_sum_bucketed(init=True)``; runs of different wires never merge.  An update that also holds Top-K
+        ``qsgd_decode_sum_bucketed(init=True)``, packed bucketed updates runs by ``(level, bucket size)`` applied
+        by ONE ``qsgd_decode_sum_bucketed_packed(init=True)``; runs of different wires never merge.  An update that also holds Top-K
         or dense layers ends the run and is applied as ``accumulate_layers`` applies it.  If staging
         update j raises, the updates before it are applied and counted, then the exception propagates:
         the accumulator holds exactly what j - 1 ``accumulate_layers`` calls would have left.  Same
@@ -351,6 +360,9 @@ class DeviceAggregator:
             if packed is True:
                 self.plan.qsgd_decode_sum_packed([b[0][0] for b in batch], level, [b[0][3] for b in batch],
                                                  y_out=self.acc, init=True)
+            elif packed and packed[0] == "bucket_packed":  # a run shares (level, d)
+                self.plan.qsgd_decode_sum_bucketed_packed([b[0][0] for b in batch], level, packed[1],
+                                                          [b[0][3] for b in batch], y_out=self.acc, init=True)
             elif packed:  # ("bucket", d): a run shares (width, level, d)
                 self.plan.qsgd_decode_sum_bucketed([b[0][0] for b in batch], width, level, packed[1],
                                                    [b[0][3] for b in batch], y_out=self.acc, init=True)
