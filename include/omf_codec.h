@@ -133,7 +133,8 @@ int32_t omf_plan_encode_strategy(const omf_plan* plan);
 /* The encoder the plan's latest encode (or fused PS step) launched: 0 register-resident +
  * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in),
  * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed), 8 the
- * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed), 9 the bucketed PS step's fused launch
+ * (omf_ps_sum_encode_bucketed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -404,6 +405,42 @@ int omf_qsgd_decode_bucketed_packed(omf_plan* plan, const uint32_t* packed, int3
 int omf_qsgd_decode_sum_bucketed_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* bnorm,
                                         int32_t nclients, int32_t levels, int64_t bucket_size, float* y_out,
                                         int32_t init, float divisor, void* stream);
+
+/*
+ * The parameter server's step for bucketed QSGD (opt-in, as the bucketed wires are): nclients bucketed payloads
+ * of one (wire, levels_in, bucket_in) summed in array order onto acc, the sum divided, and the average
+ * re-encoded with bucket norms of bucket_out — fused into ONE launch that reads every payload (and acc) once and
+ * writes the average once, whenever it can be.
+ *   acc        the sum's start (fp32 arena), or NULL: +0.  nclients == 0 needs it.
+ *   q_in / bnorm_in   HOST arrays of nclients DEVICE pointers, read at the call: client k's payload — int8
+ *              (width_in 8) or int32 (32) levels as omf_qsgd_encode_bucketed writes them, or (width_in 0) the
+ *              packed arena of omf_qsgd_encode_bucketed_packed, omf_qsgd_packed_bits(levels_in) bits a code —
+ *              and its bucket-norm arena (0 for the buckets of a tensor absent from that client's message).
+ *   sum_out    where the sum is stored: NULL (not stored), acc itself, or an arena disjoint from acc.
+ *   avg_out    the average (required): disjoint from acc, sum_out, every payload and every norm arena.
+ *   bit_width, bucket_out, pack_out, seed, offset, q_out, bnorm_out   the downlink encode: pack_out == 0
+ *              omf_qsgd_encode_bucketed's arguments, else omf_qsgd_encode_bucketed_packed's (q_out: its
+ *              packed_out).  Philox draws only.
+ * On the tensors' elements avg_out (and sum_out) hold the bytes of this sequence: omf_qsgd_decode_sum_bucketed
+ * [_packed] with init = (acc != NULL) and divisor 0 into a copy of acc, the store of that sum to sum_out,
+ * omf_div_f32 by divisor (0: no division) into avg_out.  Padding is not written, as with
+ * omf_qsgd_decode_bucketed.  q_out / bnorm_out hold the bytes of omf_qsgd_encode_bucketed[_packed](avg_out,
+ * alpha = 1, bit_width, bucket_out, seed, offset).  The call always gives those bytes: it fuses when it can and
+ * runs the existing calls otherwise — when levels_in is not a power of two, when the packed codes are wider
+ * than 16 bits, or when bit_width > 14 on the packed output.  One fused launch takes 8 clients on the int8
+ * wire, 4 on the int32 wire, 8 packed clients of codes up to 8 bits and 4 of wider ones; with more, the leading
+ * groups go through the existing sum kernels into sum_out (without it into avg_out, which the fused launch then
+ * reads in place) and the last group through the fused launch.  omf_plan_last_encoder returns 9 after a fused
+ * launch and 7 / 8 after a fallback.  No in-kernel wait: omf_plan_check has nothing to report for it.
+ * OMF_EINVAL, with nothing launched: a bad bucket size, bit_width, width_in or levels_in, nclients < 0,
+ * nclients == 0 without acc, a NULL entry, a misaligned buffer (as for the calls it replaces), avg_out
+ * overlapping acc, sum_out, a payload or a norm arena, sum_out overlapping acc partly or a payload or norm arena,
+ * a packed wire on a plan whose offsets are not multiples of 32.
+ */
+int omf_ps_sum_encode_bucketed(omf_plan* plan, const float* acc, const void* const* q_in, const float* const* bnorm_in,
+                               int32_t nclients, int32_t width_in, int32_t levels_in, int64_t bucket_in, float* sum_out,
+                               float divisor, float* avg_out, int32_t bit_width, int64_t bucket_out, int32_t pack_out,
+                               uint64_t seed, uint64_t offset, void* q_out, float* bnorm_out, void* stream);
 
 /*
  * Top-K sparsification with error feedback, all tensors of the plan in one call.

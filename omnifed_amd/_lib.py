@@ -84,6 +84,9 @@ SIGNATURES = {
     "omf_qsgd_decode_sum_bucketed_packed": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32,
                                                            _c_i32, _c_i64, _c_p, _c_i32, _c_f32, _c_p]),
     "omf_plan_set_bucket_pack": (ctypes.c_int, [_c_p, _c_i32]),
+    "omf_ps_sum_encode_bucketed": (ctypes.c_int, [_c_p, _c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32,
+                                                  _c_i32, _c_i64, _c_p, _c_f32, _c_p, _c_i32, _c_i64, _c_i32, _c_u64,
+                                                  _c_u64, _c_p, _c_p, _c_p]),
     "omf_qsgd_packed_bits": (_c_i32, [_c_i32]),
     "omf_qsgd_pack": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "omf_qsgd_decode_packed": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p]),

@@ -285,10 +285,11 @@ class Plan:
     def last_encoder(self) -> str:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
         "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms),
-        "bucketed_packed" (bucket norms, codes packed in the pass) or "none"."""
+        "bucketed_packed" (bucket norms, codes packed in the pass), "bucketed_ps" (the bucketed PS step's fused
+        launch) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
         return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {
-            5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed"}.get(code, "none")
+            5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed", 9: "bucketed_ps"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -790,6 +791,69 @@ class Plan:
         writes words i, i + 256, ... of its block, 1 two threads per 32-element group.  Identical results."""
         with self._lock:
             check(lib().omf_plan_set_bucket_pack(self._h, int(mode)), "omf_plan_set_bucket_pack")
+
+    # ------------------------------------------------------------ the bucketed PS step
+    def ps_sum_encode_bucketed(self, acc: Optional[torch.Tensor], q_in: Sequence[torch.Tensor],
+                               bnorm_in: Sequence[torch.Tensor], width_in: int, levels_in: int, bucket_in: int,
+                               divisor: Optional[float], bit_width: int, bucket_out: int, pack_out: bool = False,
+                               sum_out: Optional[torch.Tensor] = None, avg_out: Optional[torch.Tensor] = None,
+                               seed: int = 0, offset: int = 0, q_out: Optional[torch.Tensor] = None,
+                               bnorm_out: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        """The PS round's last step with bucketed QSGD (omf_ps_sum_encode_bucketed): ``sum = (acc or +0) +
+        Σ_k decode(q_in[k], bnorm_in[k])`` in list order, ``avg = sum / divisor`` (None: no division) and its
+        bucketed payload — one launch wherever the call can fuse, the bytes of ``qsgd_decode_sum_bucketed[_packed]``,
+        ``div_`` and ``qsgd_encode_bucketed[_packed]`` always.  ``width_in``: 8, 32, or 0 for packed arenas of
+        ``packed_bits(levels_in)`` bits; ``q_in`` may be empty with an ``acc``.  ``sum_out``: where ``sum`` is
+        stored (``acc`` itself, another arena, or None: not stored).  Padding of ``avg_out`` / ``sum_out`` is not
+        written.  Returns ``(avg, q_or_packed, bnorms)``."""
+        s, wi, li = int(bit_width), int(width_in), int(levels_in)
+        if not 0 <= s <= 30:
+            raise ValueError("bit_width must be in [0, 30]")
+        if wi not in (0, 8, 32):
+            raise ValueError(f"unsupported width_in={wi}")
+        q_in, bnorm_in = list(q_in), list(bnorm_in)
+        if len(q_in) != len(bnorm_in):
+            raise ValueError(f"ps_sum_encode_bucketed needs one norm arena per payload ({len(q_in)}, {len(bnorm_in)})")
+        if not q_in and acc is None:
+            raise ValueError("ps_sum_encode_bucketed needs a payload or an accumulator")
+        if q_in and li <= 0:
+            raise ValueError(f"invalid level={li}")
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        dev = self.device
+        _, nb_in = self.bucket_layout(bucket_in)
+        _, nb_out = self.bucket_layout(bucket_out)
+        qdt, qn, qal = ((torch.int32, self.packed_words(li) if q_in else 0, 4) if wi == 0 else
+                        (torch.int8, self.payload_elems(8), 4) if wi == 8 else (torch.int32, self.payload_elems(32), 16))
+        for k, (q, nm) in enumerate(zip(q_in, bnorm_in)):
+            _need(q, f"q_in[{k}]", qdt, dev, qn, qal)
+            _need(nm, f"bnorm_in[{k}]", torch.float32, dev, nb_in, 4)
+        for t, name in ((acc, "acc"), (sum_out, "sum_out")):
+            if t is not None:
+                _need(t, name, torch.float32, dev, self.arena_end, 16)
+        if avg_out is None:
+            avg_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(avg_out, "avg_out", torch.float32, dev, self.arena_end, 16)
+        width = storage_width(2 ** s)
+        if pack_out:
+            odt, on, oal = torch.int32, self.packed_words(2 ** s), 8
+        else:
+            odt, on, oal = (torch.int8 if width == 8 else torch.int32), self.payload_elems(width), 4 if width == 8 else 16
+        if q_out is None:
+            q_out = torch.empty(max(on, 1), dtype=odt, device=dev)
+        _need(q_out, "q_out", odt, dev, on, oal)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb_out)
+        n = len(q_in)
+        qp = (ctypes.c_void_p * max(n, 1))(*[q.data_ptr() for q in q_in])
+        npp = (ctypes.c_void_p * max(n, 1))(*[nm.data_ptr() for nm in bnorm_in])
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:  # the first call at a bucket size makes the plan's table
+            check(lib().omf_ps_sum_encode_bucketed(
+                self._h, _ptr(acc), qp, npp, n, wi, li, int(bucket_in), _ptr(sum_out), d, _ptr(avg_out), s,
+                int(bucket_out), 1 if pack_out else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                _ptr(q_out), _ptr(bnorm_out), ctypes.c_void_p(st)), "omf_ps_sum_encode_bucketed")
+        return avg_out, q_out, bnorm_out
 
     # ------------------------------------------------------------ bit-packed wire (opt-in)
     def packed_words(self, levels: int) -> int:

@@ -192,6 +192,7 @@ enum Encoder : int32_t {
   kEncH16 = 6,          // 16-bit arena (omf_qsgd_h16.hip): never choose_encoder's, the entry point's
   kEncBucketed = 7,     // bucket norms (omf_qsgd_bucketed.hip): never choose_encoder's, the entry point's
   kEncBucketedPacked = 8,  // bucket norms, codes packed in the pass (omf_qsgd_bucket_pack.hip): the entry point's
+  kEncBucketedPs = 9,   // the bucketed PS step's fused launch (omf_qsgd_bucket_ps.hip): the entry point's
 };
 
 struct Call {

@@ -905,6 +905,7 @@ static int encode_launch(omf_plan* p, EncCall c) {
     case kEncH16: break;  // never choose_encoder's: a 16-bit arena comes in through encode_h16_impl
     case kEncBucketed: break;  // nor this: omf_qsgd_encode_bucketed (omf_qsgd_bucketed.hip)
     case kEncBucketedPacked: break;  // nor this: omf_qsgd_encode_bucketed_packed (omf_qsgd_bucket_pack.hip)
+    case kEncBucketedPs: break;  // nor this: omf_ps_sum_encode_bucketed (omf_qsgd_bucket_ps.hip)
   }
   OMF_HIP(hipGetLastError());
   return OMF_OK;

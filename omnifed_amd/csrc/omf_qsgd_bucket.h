@@ -1,4 +1,4 @@
-// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip, omf_qsgd_bucket_pack.hip), one copy of each.  Not part of the
+// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip, omf_qsgd_bucket_pack.hip, omf_qsgd_bucket_ps.hip), one copy of each.  Not part of the
 // C ABI.  The host rules come first and are plain C++ with no HIP header; the device rules follow under
 // __HIPCC__.
 //
@@ -66,6 +66,7 @@ inline int64_t offsets(const int64_t* sizes, int32_t nt, int logd, int64_t* boff
 #ifdef __HIPCC__
 #include "omf_common.h"
 #include "omf_plan.h"
+#include "omf_qsgd_dec.h"
 #include "omf_qsgd_enc.h"
 
 namespace omf {
@@ -134,7 +135,8 @@ __device__ __forceinline__ void bucket_sums(float (&s)[V], int logd, float (*xch
 }  // namespace omf
 
 // ---------------------------------------------------------------- what the bucketed units share
-// (omf_qsgd_bucketed.hip: the int8 / int32 wire; omf_qsgd_bucket_pack.hip: the bit-packed wire).  In an
+// (omf_qsgd_bucketed.hip: the int8 / int32 wire; omf_qsgd_bucket_pack.hip: the bit-packed wire;
+// omf_qsgd_bucket_ps.hip: the PS step over both).  In an
 // unnamed namespace, as the encoders' steps they build on are (omf_qsgd_enc.h).
 
 namespace {
@@ -144,16 +146,13 @@ using namespace omf;
 constexpr const char* kBucketMisaligned = "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)";
 constexpr const char* kBucketBadSize = "bucket_size must be a power of two in [64, 4096]";
 
-// The front half of one block [b, end) of V rows of a tensor (begins at tbegin; its norms at nbase of the
-// bucket arena): x loaded once (non-temporal) and scaled into v, norm[k] the norm of the bucket that holds
-// this thread's quad of row k — computed (bucket_sums) or the caller's — and stored by the bucket's first
-// lane (of its first row).  Called by the whole workgroup.
+// The norm half of a block's front: v holds the block's V rows of values (+0 at elements past `end`); norm[k]
+// becomes the norm of the bucket that holds this thread's quad of row k — computed (bucket_sums) or the
+// caller's — and the bucket's first lane (of its first row) stores it.  Called by the whole workgroup.
 template <bool FULL, int V>
-__device__ __forceinline__ void bucket_front(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int64_t nbase,
-                                             int logd, float (*xch)[kWaves], float4 (&v)[V], float (&norm)[V]) {
+__device__ __forceinline__ void bucket_norms(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int64_t nbase,
+                                             int logd, float (*xch)[kWaves], const float4 (&v)[V], float (&norm)[V]) {
   const int tid = (int)threadIdx.x;
-  load_f4<V, FULL, true>(a.x, b, end, v);  // read once: non-temporal
-  scale_f4<V>(v, a);
   const int64_t rel = (b - tbegin) + 4 * tid;  // this thread's row 0, from the tensor's begin
   if (a.norm_in) {  // the caller's norms (uniform branch)
 #pragma unroll
@@ -178,6 +177,17 @@ __device__ __forceinline__ void bucket_front(const EncArgs& a, int64_t b, int64_
       if (FULL || b + 4 * ((int64_t)k * kThreads + tid) < end) a.norm_out[nbase + ((rel + 1024 * k) >> logd)] = norm[k];
     }
   }
+}
+
+// The front half of one block [b, end) of V rows of a tensor (begins at tbegin; its norms at nbase of the
+// bucket arena), the encoders' source: x loaded once (non-temporal) and scaled into v, then bucket_norms.  (The
+// PS step's source is K clients' payloads: omf_qsgd_bucket_ps.hip.)
+template <bool FULL, int V>
+__device__ __forceinline__ void bucket_front(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int64_t nbase,
+                                             int logd, float (*xch)[kWaves], float4 (&v)[V], float (&norm)[V]) {
+  load_f4<V, FULL, true>(a.x, b, end, v);  // read once: non-temporal
+  scale_f4<V>(v, a);
+  bucket_norms<FULL, V>(a, b, end, tbegin, nbase, logd, xch, v, norm);
 }
 
 // Quantise V rows of the block at b against each row's own norm: quant_store (omf_qsgd_enc.h) with a norm per
@@ -206,6 +216,84 @@ __device__ __forceinline__ void quant_rows(const float4 (&v)[V], const EncArgs& 
       int32_t qq[4];
       qsgd_quad(v[k], uu[sl], dv, a.levels, !(norm[k] != 0.0f), qq);
       sink(k, e, qq);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- the packed wire's back half
+constexpr int kPackRows = 4;                           // rows of 1024 elements per workgroup
+constexpr int kPackBlkElems = kPackRows * 4 * kThreads;  // 4096
+constexpr int kPackBlkGroups = kPackBlkElems / 32;     // 128
+
+// The back half of one block [b0, end) of tensor `tensor` on the bit-packed wire: the rows' levels (quant_rows)
+// as codes into the LDS tile, one barrier, the block's words out.
+// tile: kPackBlkElems / 4 8-byte fragment slots (slot k 256 + tid: the quad of row k, lane tid; group g's are
+// slots 8 g .. 8 g + 7), or WIDE kPackBlkElems dwords (one per code, in element order).
+template <bool HAS_U, bool FULL, bool WIDE>
+__device__ __forceinline__ void pack_rows(const float4 (&v)[kPackRows], const float (&norm)[kPackRows], const EncArgs& a,
+                                          int64_t b0, int64_t end, int64_t tbegin, int32_t tensor, uint32_t* tile,
+                                          int bits, int32_t L, int mode) {
+  const int tid = (int)threadIdx.x;
+  uint64_t* frag = reinterpret_cast<uint64_t*>(tile);
+  if (!FULL) {  // quads past the end hold code 0 (quant_rows skips them)
+#pragma unroll
+    for (int k = 0; k < kPackRows; ++k) {
+      if (b0 + 4 * ((int64_t)k * kThreads + tid) < end) continue;
+      if (WIDE) *reinterpret_cast<uint4*>(tile + 4 * (k * kThreads + tid)) = make_uint4(0u, 0u, 0u, 0u);
+      else frag[k * kThreads + tid] = 0ull;
+    }
+  }
+  quant_rows<HAS_U, FULL, kPackRows>(v, a, b0, end, tbegin, tensor, norm, [&](int k, int64_t e, const int32_t (&qq)[4]) {
+    uint32_t code[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) code[c] = (FULL || e + c < end) ? qsgd_code(qq[c], L) : 0u;  // code 0 past the end
+    if (WIDE) {
+      *reinterpret_cast<uint4*>(tile + 4 * (k * kThreads + tid)) = make_uint4(code[0], code[1], code[2], code[3]);
+    } else {  // the quad's fragment: 4 b <= 64 bits
+      frag[k * kThreads + tid] = (uint64_t)code[0] | ((uint64_t)code[1] << bits) | ((uint64_t)code[2] << (2 * bits)) |
+                                 ((uint64_t)code[3] << (3 * bits));
+    }
+  });
+  __syncthreads();
+  const int groups = FULL ? kPackBlkGroups : (int)((end - b0 + 31) >> 5);
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.q) + (b0 >> 5) * (int64_t)bits;  // b0 is a multiple of 32
+  if (WIDE || mode == 0) {
+    // thread i writes words i, i + 256, ...: word W is word W - g b of group g = floor(W / b)
+    const int ub = WIDE ? bits : 4 * bits, n = WIDE ? 32 : 8, span = ub < 16 ? 4 : 3;
+    const float inv_b = 1.0f / (float)bits, inv_ub = 1.0f / (float)ub;
+    const int words = groups * bits;
+    for (int W = tid; W < words; W += kThreads) {
+      const int g = (int)(((float)W + 0.5f) * inv_b);  // exact: W < 4096, b <= 32 (group_word's argument)
+      const uint32_t word = group_word(W - g * bits, ub, inv_ub, n, span, [&](int j) {
+        return WIDE ? (uint64_t)tile[32 * g + j] : frag[8 * g + j];
+      });
+      store_nt(out + W, word);
+    }
+    return;
+  }
+  // two threads per group, each its half of the group's b words: the fragments walked in halves of 2 b <= 32
+  // bits through a 64-bit accumulator, as qsgd_pack walks its levels
+  const int g = tid >> 1;
+  if (g >= groups) return;
+  const int half = (bits + 1) >> 1;
+  const int w0 = (tid & 1) ? half : 0, w1 = (tid & 1) ? bits : half;
+  const int hb = 2 * bits;
+  const uint64_t hm = (1ull << hb) - 1ull;
+  uint64_t acc = 0;
+  int nb = 0, w = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint64_t f = frag[8 * g + j];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      acc |= (h ? f >> hb : f & hm) << nb;
+      nb += hb;
+      if (nb >= 32) {
+        if (w >= w0 && w < w1) store_nt(out + g * bits + w, (uint32_t)acc);
+        ++w;
+        acc >>= 32;
+        nb -= 32;
+      }
     }
   }
 }

@@ -51,83 +51,19 @@ namespace {
 
 // ---------------------------------------------------------------- encoder
 
-constexpr int kRows = 4;                       // rows of 1024 elements per workgroup
-constexpr int kBlkElems = kRows * 4 * kThreads;  // 4096
-constexpr int kBlkGroups = kBlkElems / 32;     // 128
+constexpr int kRows = kPackRows;          // rows of 1024 elements per workgroup
+constexpr int kBlkElems = kPackBlkElems;  // 4096
 
-// One block [b0, end) of tensor `tensor`: norms, levels, codes into the LDS tile, the block's words out.
-// tile: kBlkElems / 4 8-byte fragment slots (slot k 256 + tid: the quad of row k, lane tid; group g's are
-// slots 8 g .. 8 g + 7), or WIDE kBlkElems dwords (one per code, in element order).
+// One block [b0, end) of tensor `tensor`: norms (bucket_front), then levels, codes into the LDS tile and the
+// block's words out (pack_rows, omf_qsgd_bucket.h).
 template <bool HAS_U, bool FULL, bool WIDE>
 __device__ __forceinline__ void pack_block(const EncArgs& a, int64_t b0, int64_t end, int64_t tbegin, int32_t tensor,
                                            int64_t nbase, int logd, float (*xch)[kWaves], uint32_t* tile, int bits,
                                            int32_t L, int mode) {
-  const int tid = (int)threadIdx.x;
-  uint64_t* frag = reinterpret_cast<uint64_t*>(tile);
   float4 v[kRows];
   float norm[kRows];
   bucket_front<FULL, kRows>(a, b0, end, tbegin, nbase, logd, xch, v, norm);
-  if (!FULL) {  // quads past the end hold code 0 (quant_rows skips them)
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-      if (b0 + 4 * ((int64_t)k * kThreads + tid) < end) continue;
-      if (WIDE) *reinterpret_cast<uint4*>(tile + 4 * (k * kThreads + tid)) = make_uint4(0u, 0u, 0u, 0u);
-      else frag[k * kThreads + tid] = 0ull;
-    }
-  }
-  quant_rows<HAS_U, FULL, kRows>(v, a, b0, end, tbegin, tensor, norm, [&](int k, int64_t e, const int32_t (&qq)[4]) {
-    uint32_t code[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) code[c] = (FULL || e + c < end) ? qsgd_code(qq[c], L) : 0u;  // code 0 past the end
-    if (WIDE) {
-      *reinterpret_cast<uint4*>(tile + 4 * (k * kThreads + tid)) = make_uint4(code[0], code[1], code[2], code[3]);
-    } else {  // the quad's fragment: 4 b <= 64 bits
-      frag[k * kThreads + tid] = (uint64_t)code[0] | ((uint64_t)code[1] << bits) | ((uint64_t)code[2] << (2 * bits)) |
-                                 ((uint64_t)code[3] << (3 * bits));
-    }
-  });
-  __syncthreads();
-  const int groups = FULL ? kBlkGroups : (int)((end - b0 + 31) >> 5);
-  uint32_t* out = reinterpret_cast<uint32_t*>(a.q) + (b0 >> 5) * (int64_t)bits;  // b0 is a multiple of 32
-  if (WIDE || mode == 0) {
-    // thread i writes words i, i + 256, ...: word W is word W - g b of group g = floor(W / b)
-    const int ub = WIDE ? bits : 4 * bits, n = WIDE ? 32 : 8, span = ub < 16 ? 4 : 3;
-    const float inv_b = 1.0f / (float)bits, inv_ub = 1.0f / (float)ub;
-    const int words = groups * bits;
-    for (int W = tid; W < words; W += kThreads) {
-      const int g = (int)(((float)W + 0.5f) * inv_b);  // exact: W < 4096, b <= 32 (group_word's argument)
-      const uint32_t word = group_word(W - g * bits, ub, inv_ub, n, span, [&](int j) {
-        return WIDE ? (uint64_t)tile[32 * g + j] : frag[8 * g + j];
-      });
-      store_nt(out + W, word);
-    }
-    return;
-  }
-  // two threads per group, each its half of the group's b words: the fragments walked in halves of 2 b <= 32
-  // bits through a 64-bit accumulator, as qsgd_pack walks its levels
-  const int g = tid >> 1;
-  if (g >= groups) return;
-  const int half = (bits + 1) >> 1;
-  const int w0 = (tid & 1) ? half : 0, w1 = (tid & 1) ? bits : half;
-  const int hb = 2 * bits;
-  const uint64_t hm = (1ull << hb) - 1ull;
-  uint64_t acc = 0;
-  int nb = 0, w = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint64_t f = frag[8 * g + j];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      acc |= (h ? f >> hb : f & hm) << nb;
-      nb += hb;
-      if (nb >= 32) {
-        if (w >= w0 && w < w1) store_nt(out + g * bits + w, (uint32_t)acc);
-        ++w;
-        acc >>= 32;
-        nb -= 32;
-      }
-    }
-  }
+  pack_rows<HAS_U, FULL, WIDE>(v, norm, a, b0, end, tbegin, tensor, tile, bits, L, mode);
 }
 
 // LOGD: log2 d at compile time, or 0: the kernel argument (the WIDE instances).

@@ -165,6 +165,26 @@ __device__ __forceinline__ uint32_t group_word(int w, int ub, float inv_ub, int 
   return word;
 }
 
+// The mirror image of group_word: the four codes of quad f (elements 4 f .. 4 f + 3, f = 0 .. 7) of a 32-element
+// group from the group's b words, b <= 16.  The quad's fragment is bits [4 b f, 4 b (f + 1)) of the words'
+// concatenation: it starts inside word w0 = floor(4 b f / 32) at bit sh (a multiple of 4) and ends before bit
+// sh + 64 <= 92, so it lies in words w0 .. w0 + 2; every code (b <= 16 bits) is read through one 64-bit window,
+// the one over words w0, w0 + 1 where it starts below bit 32 and the one over w0 + 1, w0 + 2 otherwise.  A
+// window's word past the group's last (index clamped to b - 1) holds no bit of the fragment.  word(i): word i of
+// the group.
+template <class Word>
+__device__ __forceinline__ void group_quad(int f, int b, Word word, uint32_t (&code)[4]) {
+  const int bit0 = 4 * b * f, w0 = bit0 >> 5, sh = bit0 & 31;
+  const uint32_t x0 = word(w0), x1 = word(min(w0 + 1, b - 1)), x2 = word(min(w0 + 2, b - 1));
+  const uint64_t lo = (uint64_t)x0 | ((uint64_t)x1 << 32), hi = (uint64_t)x1 | ((uint64_t)x2 << 32);
+  const uint32_t mask = (1u << b) - 1u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int p = sh + j * b;  // < 28 + 3 * 16 + 1
+    code[j] = (uint32_t)(p < 32 ? lo >> p : hi >> (p - 32)) & mask;
+  }
+}
+
 // A thread's 32-element group at e0 in a workgroup of kGroupBlk elements (two blocks of the plan's decoder
 // table): the whole workgroup inside one tensor (both table blocks marked inside the same tensor), or the
 // group's own tensor found from the block's first one (offsets are multiples of 32: a group never spans two

@@ -348,6 +348,10 @@ class DeviceAggregator:
         the accumulator holds exactly what j - 1 ``accumulate_layers`` calls would have left.  Same
         bytes and counters as one ``accumulate_layers`` call per update."""
         self._check_fresh()
+        self._apply_many(((self._stage_update(layers), number_samples) for layers, number_samples in updates), max_batch)
+
+    def _apply_many(self, staged_updates, max_batch: int = 8):
+        """``accumulate_many``'s runs over ``(staged update, number_samples)`` pairs (an iterator may stage as it goes)."""
         max_batch = max(int(max_batch), 1)
         run: List[tuple] = []  # [(q_args, number_samples)] of one (width, level)
 
@@ -373,8 +377,7 @@ class DeviceAggregator:
             self.total_samples += sum(int(ns) for _, ns in batch)
 
         try:
-            for layers, number_samples in updates:
-                staged = self._stage_update(layers)
+            for staged, number_samples in staged_updates:
                 q_args, t_args, adds = staged
                 if q_args is not None and t_args is None and not adds:
                     if run and (run[0][0][1:3] != q_args[1:3] or run[0][0][4] != q_args[4] or len(run) >= max_batch):
@@ -449,8 +452,10 @@ class DeviceAggregator:
         total = self.total_samples if total_samples is None else int(total_samples)
         if self.avg is None:
             self.avg = torch.empty_like(self.acc)
+        if self._bucketed_step_serves(compressor, total):  # bucket norms: one launch that reads the accumulator once
+            return self._bucketed_step([], total, compressor, False)
         if (not isinstance(compressor, QSGDQuantCompression) or not self.compute_mean
-                or compressor.bucket_size is not None  # bucket norms: divide, then the bucketed encode
+                or compressor.bucket_size is not None  # bucket norms, not served above: divide, then the bucketed encode
                 or compressor.rng != "philox"):  # parity mode draws MT19937 uniforms on the host
             self.avg.copy_(self.acc)
             if self.compute_mean:
@@ -493,6 +498,8 @@ class DeviceAggregator:
 
         self._check_fresh()
         layers = list(layers)
+        if self._bucketed_step_serves(compressor, self.total_samples + int(number_samples)):
+            return self.sum_apply_encode([(layers, number_samples)], compressor, keep_sum=keep_sum)
         last: Dict[str, object] = {}
         for L in layers:
             _validate_layer(L)
@@ -542,6 +549,85 @@ class DeviceAggregator:
         for n, L in zip(self.names, got):
             out.append(L if L is not None and int(np.prod(self.shapes[n])) > 0 else _encode_dense_layer(n, avg[n]))
         return avg, out
+
+    # The fused bucketed step (omf_ps_sum_encode_bucketed) is the default wherever it was measured ahead of the
+    # sequence it replaces; False routes bucketed rounds through that sequence again.
+    fuse_bucketed_step = True
+
+    def _bucketed_step_serves(self, compressor, total) -> bool:
+        """A round that ends in ``_bucketed_step``: a bucketed (packed or not) Philox QSGD compressor, the mean over
+        a non-zero total, and every tensor non-empty (the downlink plan ``encode_updates_dict`` would build for
+        the average is then the aggregator's own, so layout and Philox counters agree)."""
+        from .hybrid.compression.qsgd import QSGDQuantCompression
+        return (self.fuse_bucketed_step and isinstance(compressor, QSGDQuantCompression)
+                and compressor.bucket_size is not None and compressor.rng == "philox" and self.compute_mean
+                and 0 <= compressor.s <= 30 and float(total) != 0.0 and bool(self.names)
+                and all(numel(self.shapes[n]) > 0 for n in self.names))
+
+    def _bucketed_step(self, run, total, compressor, keep_sum: bool):
+        """``acc + Σ decode(run)``, its average over ``total`` and the average's bucketed downlink in one call
+        (``Plan.ps_sum_encode_bucketed``).  ``run``: staged ``q_args`` of like bucketed updates, possibly none (the
+        accumulator alone).  Same return as ``apply_and_encode``."""
+        from .hybrid.communicator.global_grpc_compression import (_encode_dense_layer, _host_memory_policy,
+                                                                  qsgd_bucketed_layers_from_arena)
+        _host_memory_policy()
+        if self.avg is None:
+            self.avg = torch.empty_like(self.acc)
+        d_out, s = compressor.bucket_size, compressor.s
+        if run:
+            _, width, level, _, packed = run[0]
+            wire, d_in = (0 if packed[0] == "bucket_packed" else width), packed[1]
+        else:
+            wire, level, d_in = 8, 1, d_out
+        _, q, bn = self.plan.ps_sum_encode_bucketed(
+            self.acc, [a[0] for a in run], [a[3] for a in run], wire, level, d_in, float(total), s, d_out,
+            pack_out=compressor.bucket_packed, sum_out=self.acc if (keep_sum and run) else None, avg_out=self.avg,
+            seed=compressor.philox_key(), offset=compressor._next_call())
+        avg = {n: self._avg_slice(n).view(self.shapes[n]) for n in self.names}
+        got = qsgd_bucketed_layers_from_arena(self.plan, q, bn, self.names, [self.shapes[n] for n in self.names], 2**s,
+                                              d_out, packed=compressor.bucket_packed)
+        return avg, [L if L is not None else _encode_dense_layer(n, avg[n]) for n, L in zip(self.names, got)]
+
+    def sum_apply_encode(self, updates, compressor, keep_sum: bool = True, max_batch: int = 8):
+        """``accumulate_many(updates)`` and ``apply_and_encode(compressor)`` with the round's end in one launch:
+        every update is staged first, all but the trailing run of like bucketed updates (QSGD-only, one wire,
+        width, level and bucket size; at most ``max_batch``) are applied as ``accumulate_many`` applies them, and
+        the trailing run is summed onto the accumulator, averaged and re-encoded by ``_bucketed_step`` — the
+        average is never re-read.  ``keep_sum`` as in ``accumulate_apply_encode``.  Same bytes, counters and
+        return as the two calls; anything that cannot fuse (another compressor, a trailing update with Top-K or
+        dense layers, a zero total) takes them.  If staging update j raises, the updates before it are applied
+        and counted, then the exception propagates, as in ``accumulate_many``."""
+        self._check_fresh()
+        updates = list(updates)
+        if not self._bucketed_step_serves(compressor, 1):
+            self.accumulate_many(updates, max_batch)
+            return self.apply_and_encode(compressor)
+        staged: List[tuple] = []
+        try:
+            for layers, number_samples in updates:
+                staged.append((self._stage_update(layers), number_samples))
+        except Exception:
+            self._apply_many(staged, max_batch)
+            raise
+
+        def bucketed_only(st):
+            return st[0] is not None and st[1] is None and not st[2] and isinstance(st[0][4], tuple)
+
+        tail = len(staged)
+        while (tail > 0 and len(staged) - tail < max(int(max_batch), 1) and bucketed_only(staged[tail - 1][0])
+               and staged[tail - 1][0][0][1:3] == staged[-1][0][0][1:3] and staged[tail - 1][0][0][4] == staged[-1][0][0][4]):
+            tail -= 1
+        total = self.total_samples + sum(int(ns) for _, ns in staged)
+        if tail == len(staged) or not self._bucketed_step_serves(compressor, total):
+            self._apply_many(staged, max_batch)
+            return self.apply_and_encode(compressor)
+        self._apply_many(staged[:tail], max_batch)
+        out = self._bucketed_step([st[0] for st, _ in staged[tail:]], total, compressor, keep_sum)
+        self.update_count += len(staged) - tail
+        self.total_samples = total
+        if not keep_sum:
+            self._stale = True
+        return out
 
     def apply(self, total_samples: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """_apply_model_updates (global_grpc_server.py:155-171): acc / total_samples per tensor."""
