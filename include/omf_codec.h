@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 120
+#define OMF_ABI_VERSION 121
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -134,7 +134,8 @@ int32_t omf_plan_encode_strategy(const omf_plan* plan);
  * two-pass, 1 two-pass, 2 ring, 3 bracketed, 4 grid, 5 levels with caller norms (norm_in),
  * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed), 8 the
  * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed), 9 the bucketed PS step's fused launch
- * (omf_ps_sum_encode_bucketed); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * (omf_ps_sum_encode_bucketed), 10 / 11 the bucketed encoders of a 16-bit arena (omf_qsgd_encode_bucketed_h16 /
+ * omf_qsgd_encode_bucketed_packed_h16); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -299,7 +300,8 @@ int omf_qsgd_decode_sum(omf_plan* plan, const void* const* q, const float* const
  * bucket, levels against norm_b (all zero for a zero norm_b), decode fl32(fl32(norm_b * q) / fl32(levels)).
  * Tensor t has ceil(sizes[t] / d) norms; a bucket-norm arena holds them tensor after tensor, bucket after
  * bucket (omf_qsgd_bucket_count entries, fp32).  The draws (u, or Philox from seed / offset) and the payload
- * arena are omf_qsgd_encode's.  fp32 arenas only.  A bucket's norm bits depend only on its values and d
+ * arena are omf_qsgd_encode's.  These calls read fp32 arenas; bf16 / fp16 arenas are encoded in place by the
+ * _h16 calls below.  A bucket's norm bits depend only on its values and d
  * (fixed summation order: omnifed_amd/csrc/omf_qsgd_bucket.h).  One launch per call, x read once, no
  * in-kernel wait (omf_plan_check has nothing to report for it); the first call at a bucket size on a plan
  * uploads one small table (synchronous), later calls neither allocate nor synchronise.
@@ -381,7 +383,8 @@ int omf_qsgd_decode_sum_packed(omf_plan* plan, const uint32_t* const* packed, co
  * bucket-norm arena, the same bits).  Codes: omf_qsgd_pack's arena (code q + L in b = omf_qsgd_packed_bits(L)
  * bits, LSB first, tensor t at word offsets[t] * b / 32 of ceil(arena_end / 32) * b words, code 0 after a
  * tensor's last element inside its last group, groups without a tensor element not written); every tensor
- * offset a multiple of 32 elements, else OMF_EINVAL.  fp32 arenas only.
+ * offset a multiple of 32 elements, else OMF_EINVAL.  fp32 arenas here; bf16 / fp16 arenas:
+ * omf_qsgd_encode_bucketed_packed_h16.
  *   omf_qsgd_encode_bucketed_packed      ONE launch that reads x once and writes the words that
  *                                        omf_qsgd_encode_bucketed followed by omf_qsgd_pack writes (L =
  *                                        2^bit_width, bit_width 0 .. 30, on every written group) and the norms
@@ -405,6 +408,30 @@ int omf_qsgd_decode_bucketed_packed(omf_plan* plan, const uint32_t* packed, int3
 int omf_qsgd_decode_sum_bucketed_packed(omf_plan* plan, const uint32_t* const* packed, const float* const* bnorm,
                                         int32_t nclients, int32_t levels, int64_t bucket_size, float* y_out,
                                         int32_t init, float divisor, void* stream);
+
+/*
+ * The bucketed encoders for tensors whose dtype is bf16 or fp16, without an fp32 upcast arena.  x16 is as in
+ * omf_qsgd_encode_h16: the tensors' own bf16 (value_format 1) or fp16 (2) bit patterns at the plan's offsets in
+ * ELEMENTS, 16-byte aligned, arena_end elements long; nothing outside the tensors' ranges is read.  The values
+ * are widened exactly and everything after that is fp32: xs = fl32(alpha * float(x16)), norm_b and the levels as
+ * omf_qsgd_encode_bucketed computes them — NOTHING is rounded to the value format (unlike omf_qsgd_encode_h16,
+ * which rounds where the reference's reduced-precision ops do; the reference has no buckets to match, and a
+ * quotient rounded to bf16 would bias the quantiser).  bnorm_out and q_out / packed_out therefore hold the bits
+ * of omf_qsgd_encode_bucketed / omf_qsgd_norms_bucketed / omf_qsgd_encode_bucketed_packed on the exact fp32
+ * upcast of the arena, and the wire, the decoders and the PS step are unchanged.  ONE launch per call that reads
+ * x16 once (2 bytes per element read, against 11 moved through an upcast arena), no in-kernel wait, no
+ * allocation after the first call at a bucket size.  value_format other than 1 or 2: OMF_EINVAL; every other
+ * argument, check and error is the fp32 sibling's.
+ */
+int omf_qsgd_encode_bucketed_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, int32_t bit_width,
+                                 int64_t bucket_size, const float* u, uint64_t seed, uint64_t offset,
+                                 const float* bnorm_in, void* q_out, float* bnorm_out, void* stream);
+int omf_qsgd_norms_bucketed_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha, int64_t bucket_size,
+                                float* bnorm_out, void* stream);
+int omf_qsgd_encode_bucketed_packed_h16(omf_plan* plan, const void* x16, int32_t value_format, float alpha,
+                                        int32_t bit_width, int64_t bucket_size, const float* u, uint64_t seed,
+                                        uint64_t offset, const float* bnorm_in, uint32_t* packed_out, float* bnorm_out,
+                                        void* stream);
 
 /*
  * The parameter server's step for bucketed QSGD (opt-in, as the bucketed wires are): nclients bucketed payloads

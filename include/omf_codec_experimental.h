@@ -66,7 +66,9 @@ int omf_plan_set_h16(omf_plan* plan, int32_t wide_loads, int32_t rows);
 /* The bucketed encoder's rows of 1024 elements per workgroup (omf_qsgd_encode_bucketed;
  * scripts/bucketed_encode_ab.py times them): 4 (the default: measured fastest), 8 or 16; static_d != 0 (the
  * default: measured no slower at any bucket size, faster from 1024 up): the 4-row kernels with the bucket size
- * at compile time, else as a kernel argument (8 and 16 rows always).  Identical norms and payloads. */
+ * at compile time, else as a kernel argument (8 and 16 rows always).  Identical norms and payloads.  The 16-bit
+ * arena's encoder (omf_qsgd_encode_bucketed_h16; scripts/bucketed_h16_ab.py) runs 8 rows when asked for 8, else
+ * its default 4, the bucket size at compile time either way; its packed sibling always 4. */
 int omf_plan_set_bucket_rows(omf_plan* plan, int32_t rows, int32_t static_d);
 /* The packed bucketed encoder's output assignment (omf_qsgd_encode_bucketed_packed, code widths up to 16 bits;
  * scripts/bucketed_packed_ab.py times them): 0 thread i of a workgroup writes words i, i + 256, ... of its

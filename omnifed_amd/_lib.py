@@ -84,6 +84,11 @@ SIGNATURES = {
     "omf_qsgd_decode_sum_bucketed_packed": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32,
                                                            _c_i32, _c_i64, _c_p, _c_i32, _c_f32, _c_p]),
     "omf_plan_set_bucket_pack": (ctypes.c_int, [_c_p, _c_i32]),
+    "omf_qsgd_encode_bucketed_h16": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_f32, _c_i32, _c_i64, _c_p, _c_u64, _c_u64,
+                                                    _c_p, _c_p, _c_p, _c_p]),
+    "omf_qsgd_norms_bucketed_h16": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_f32, _c_i64, _c_p, _c_p]),
+    "omf_qsgd_encode_bucketed_packed_h16": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_f32, _c_i32, _c_i64, _c_p, _c_u64,
+                                                           _c_u64, _c_p, _c_p, _c_p, _c_p]),
     "omf_ps_sum_encode_bucketed": (ctypes.c_int, [_c_p, _c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32,
                                                   _c_i32, _c_i64, _c_p, _c_f32, _c_p, _c_i32, _c_i64, _c_i32, _c_u64,
                                                   _c_u64, _c_p, _c_p, _c_p]),
@@ -128,7 +133,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 120 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 121 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

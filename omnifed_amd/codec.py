@@ -138,6 +138,15 @@ def _h16_format(x: torch.Tensor, value_format: int) -> int:
     return fmt
 
 
+def _bucket_format(x) -> int:
+    """The value format of a bucketed encode's arena: 0 for fp32, the 16-bit arena's own for bf16 / fp16; any other
+    dtype raises ``ValueError``."""
+    dt = getattr(x, "dtype", None)
+    if dt is not torch.float32 and dt not in H16_FORMATS:
+        raise ValueError(f"bucketed QSGD encodes float32, bfloat16 and float16 arenas, not {dt}")
+    return H16_FORMATS.get(dt, 0)
+
+
 DECODE_BLOCK = 4096  # elements per decode block (omf_qsgd_decode_range granularity)
 
 
@@ -286,10 +295,11 @@ class Plan:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
         "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms),
         "bucketed_packed" (bucket norms, codes packed in the pass), "bucketed_ps" (the bucketed PS step's fused
-        launch) or "none"."""
+        launch), "bucketed_h16" / "bucketed_packed_h16" (the bucketed encoders of a bf16 / fp16 arena) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
         return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {
-            5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed", 9: "bucketed_ps"}.get(code, "none")
+            5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed", 9: "bucketed_ps",
+            10: "bucketed_h16", 11: "bucketed_packed_h16"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -582,9 +592,10 @@ class Plan:
                              bnorm_in: Optional[torch.Tensor] = None, stream: Optional[int] = None):
         """omf_qsgd_encode_bucketed: ``qsgd_encode`` with one norm per bucket of ``bucket_size`` consecutive
         elements of a tensor; returns ``(q, bnorms)``, ``bnorms`` the plan's bucket-norm arena
-        (``bucket_layout``).  fp32 arenas only: a bf16 / fp16 ``x`` raises ``ValueError``."""
-        if getattr(x, "dtype", None) in H16_FORMATS:
-            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        (``bucket_layout``).  A bf16 / fp16 ``x`` is the tensors' own 16-bit arena (the plan's offsets, in
+        elements), read in place (omf_qsgd_encode_bucketed_h16): the norms and payload of its exact fp32 upcast,
+        nothing rounded to the 16-bit format."""
+        fmt = _bucket_format(x)
         _, nb = self.bucket_layout(bucket_size)
         s = int(bit_width)
         if not 0 <= s <= 30:
@@ -592,7 +603,7 @@ class Plan:
         width = storage_width(2 ** s)
         qdt = torch.int8 if width == 8 else torch.int32
         dev = self.device
-        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        _need(x, "x", x.dtype, dev, self.arena_end, 16)
         if q_out is None:
             q_out = torch.empty(self.payload_elems(width), dtype=qdt, device=dev)
         _need(q_out, "q_out", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
@@ -602,25 +613,33 @@ class Plan:
         if bnorm_in is not None:
             _need(bnorm_in, "bnorm_in", torch.float32, dev, nb, 4)
         st = stream if stream is not None else _stream(dev)
+        tail = (s, int(bucket_size), _ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                _ptr(bnorm_in), _ptr(q_out), _ptr(bnorm_out), ctypes.c_void_p(st))
         with self._lock:
-            check(lib().omf_qsgd_encode_bucketed(self._h, _ptr(x), float(alpha), s, int(bucket_size), _ptr(u),
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
-                                                 _ptr(bnorm_in), _ptr(q_out), _ptr(bnorm_out), ctypes.c_void_p(st)),
-                  "omf_qsgd_encode_bucketed")
+            if fmt:
+                check(lib().omf_qsgd_encode_bucketed_h16(self._h, _ptr(x), fmt, float(alpha), *tail),
+                      "omf_qsgd_encode_bucketed_h16")
+            else:
+                check(lib().omf_qsgd_encode_bucketed(self._h, _ptr(x), float(alpha), *tail), "omf_qsgd_encode_bucketed")
         return q_out, bnorm_out
 
     def qsgd_norms_bucketed(self, x: torch.Tensor, bucket_size: int, alpha: float = 1.0,
                             bnorm_out: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
-        """The bucket norms alone (omf_qsgd_norms_bucketed): the bits ``qsgd_encode_bucketed`` writes."""
-        if getattr(x, "dtype", None) in H16_FORMATS:
-            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        """The bucket norms alone (omf_qsgd_norms_bucketed, or omf_qsgd_norms_bucketed_h16 for a bf16 / fp16
+        arena): the bits ``qsgd_encode_bucketed`` writes."""
+        fmt = _bucket_format(x)
         _, nb = self.bucket_layout(bucket_size)
-        _need(x, "x", torch.float32, self.device, self.arena_end, 16)
+        _need(x, "x", x.dtype, self.device, self.arena_end, 16)
         bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
         st = stream if stream is not None else _stream(self.device)
         with self._lock:
-            check(lib().omf_qsgd_norms_bucketed(self._h, _ptr(x), float(alpha), int(bucket_size), _ptr(bnorm_out),
-                                                ctypes.c_void_p(st)), "omf_qsgd_norms_bucketed")
+            if fmt:
+                check(lib().omf_qsgd_norms_bucketed_h16(self._h, _ptr(x), fmt, float(alpha), int(bucket_size),
+                                                        _ptr(bnorm_out), ctypes.c_void_p(st)),
+                      "omf_qsgd_norms_bucketed_h16")
+            else:
+                check(lib().omf_qsgd_norms_bucketed(self._h, _ptr(x), float(alpha), int(bucket_size), _ptr(bnorm_out),
+                                                    ctypes.c_void_p(st)), "omf_qsgd_norms_bucketed")
         return bnorm_out
 
     def qsgd_decode_bucketed(self, q: torch.Tensor, width: int, levels: int, bucket_size: int, bnorm: torch.Tensor,
@@ -690,7 +709,8 @@ class Plan:
     def set_bucket_rows(self, rows: int = 4, static_d: bool = True) -> None:
         """Experiment hook of the bucketed encoder (omf_plan_set_bucket_rows): the defaults, or 8 / 16 rows (and, at 4 rows, the
         bucket size as a kernel argument instead of at compile time); rows of
-        1024 elements per workgroup.  Identical results."""
+        1024 elements per workgroup.  A bf16 / fp16 arena's encoder runs 8 rows when asked for 8, else 4.  Identical
+        results."""
         with self._lock:
             check(lib().omf_plan_set_bucket_rows(self._h, int(rows), 1 if static_d else 0), "omf_plan_set_bucket_rows")
 
@@ -702,16 +722,15 @@ class Plan:
                                     bnorm_in: Optional[torch.Tensor] = None, stream: Optional[int] = None):
         """omf_qsgd_encode_bucketed_packed: ``qsgd_encode_bucketed`` whose codes leave the encode pass already
         packed — the words of ``qsgd_pack(qsgd_encode_bucketed(...))`` on every written group, in one launch;
-        returns ``(packed, bnorms)``.  ``packed_out`` is written only where a tensor has elements.  fp32 arenas
-        only: a bf16 / fp16 ``x`` raises ``ValueError``."""
-        if getattr(x, "dtype", None) in H16_FORMATS:
-            raise ValueError(f"bucketed QSGD encodes fp32 arenas, not {x.dtype}")
+        returns ``(packed, bnorms)``.  ``packed_out`` is written only where a tensor has elements.  A bf16 /
+        fp16 ``x`` is read in place, as by ``qsgd_encode_bucketed`` (omf_qsgd_encode_bucketed_packed_h16)."""
+        fmt = _bucket_format(x)
         _, nb = self.bucket_layout(bucket_size)
         s = int(bit_width)
         if not 0 <= s <= 30:
             raise ValueError("bit_width must be in [0, 30]")
         dev = self.device
-        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        _need(x, "x", x.dtype, dev, self.arena_end, 16)
         words = self.packed_words(2 ** s)
         if packed_out is None:
             packed_out = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
@@ -722,12 +741,15 @@ class Plan:
         if bnorm_in is not None:
             _need(bnorm_in, "bnorm_in", torch.float32, dev, nb, 4)
         st = stream if stream is not None else _stream(dev)
+        tail = (s, int(bucket_size), _ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                _ptr(bnorm_in), _ptr(packed_out), _ptr(bnorm_out), ctypes.c_void_p(st))
         with self._lock:
-            check(lib().omf_qsgd_encode_bucketed_packed(self._h, _ptr(x), float(alpha), s, int(bucket_size), _ptr(u),
-                                                        int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                        int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(bnorm_in),
-                                                        _ptr(packed_out), _ptr(bnorm_out), ctypes.c_void_p(st)),
-                  "omf_qsgd_encode_bucketed_packed")
+            if fmt:
+                check(lib().omf_qsgd_encode_bucketed_packed_h16(self._h, _ptr(x), fmt, float(alpha), *tail),
+                      "omf_qsgd_encode_bucketed_packed_h16")
+            else:
+                check(lib().omf_qsgd_encode_bucketed_packed(self._h, _ptr(x), float(alpha), *tail),
+                      "omf_qsgd_encode_bucketed_packed")
         return packed_out, bnorm_out
 
     def qsgd_decode_bucketed_packed(self, packed: torch.Tensor, levels: int, bucket_size: int, bnorm: torch.Tensor,

@@ -61,6 +61,8 @@ struct omf_plan {
   // d = 4096 0.377 ms against 0.409) and at every size on ResNet-18
   int64_t* d_boff[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int64_t bucket_nb[7] = {0, 0, 0, 0, 0, 0, 0};
+  // (the 16-bit arena's encoder, omf_qsgd_bucket_h16.hip, reads bucket_rows too: 8 rows when it is 8, else 4 — within
+  // each other's spread on Llama-400M, 4 rows 10 % faster on ResNet-18: profiles/bucketed_h16_ab.json)
   int32_t bucket_rows = 4;
   bool bucket_static_d = true;   // the 4-row kernel with d at compile time (omf_plan_set_bucket_rows)
   int32_t bucket_pack = 0;       // the packed bucketed encoder's output assignment (omf_plan_set_bucket_pack)

@@ -193,6 +193,8 @@ enum Encoder : int32_t {
   kEncBucketed = 7,     // bucket norms (omf_qsgd_bucketed.hip): never choose_encoder's, the entry point's
   kEncBucketedPacked = 8,  // bucket norms, codes packed in the pass (omf_qsgd_bucket_pack.hip): the entry point's
   kEncBucketedPs = 9,   // the bucketed PS step's fused launch (omf_qsgd_bucket_ps.hip): the entry point's
+  kEncBucketedH16 = 10,        // bucket norms from a 16-bit arena (omf_qsgd_bucket_h16.hip): the entry point's
+  kEncBucketedPackedH16 = 11,  // the same on the bit-packed wire (omf_qsgd_bucket_h16.hip): the entry point's
 };
 
 struct Call {

@@ -906,6 +906,8 @@ static int encode_launch(omf_plan* p, EncCall c) {
     case kEncBucketed: break;  // nor this: omf_qsgd_encode_bucketed (omf_qsgd_bucketed.hip)
     case kEncBucketedPacked: break;  // nor this: omf_qsgd_encode_bucketed_packed (omf_qsgd_bucket_pack.hip)
     case kEncBucketedPs: break;  // nor this: omf_ps_sum_encode_bucketed (omf_qsgd_bucket_ps.hip)
+    case kEncBucketedH16:
+    case kEncBucketedPackedH16: break;  // nor these: omf_qsgd_encode_bucketed[_packed]_h16 (omf_qsgd_bucket_h16.hip)
   }
   OMF_HIP(hipGetLastError());
   return OMF_OK;

@@ -1,4 +1,5 @@
-// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip, omf_qsgd_bucket_pack.hip, omf_qsgd_bucket_ps.hip), one copy of each.  Not part of the
+// omf_qsgd_bucket.h — the rules of bucketed QSGD (omf_qsgd_bucketed.hip, omf_qsgd_bucket_pack.hip, omf_qsgd_bucket_ps.hip,
+// omf_qsgd_bucket_h16.hip), one copy of each.  Not part of the
 // C ABI.  The host rules come first and are plain C++ with no HIP header; the device rules follow under
 // __HIPCC__.
 //
@@ -136,7 +137,7 @@ __device__ __forceinline__ void bucket_sums(float (&s)[V], int logd, float (*xch
 
 // ---------------------------------------------------------------- what the bucketed units share
 // (omf_qsgd_bucketed.hip: the int8 / int32 wire; omf_qsgd_bucket_pack.hip: the bit-packed wire;
-// omf_qsgd_bucket_ps.hip: the PS step over both).  In an
+// omf_qsgd_bucket_ps.hip: the PS step over both; omf_qsgd_bucket_h16.hip: both wires from a 16-bit arena).  In an
 // unnamed namespace, as the encoders' steps they build on are (omf_qsgd_enc.h).
 
 namespace {

@@ -3,7 +3,7 @@
 //
 // The element math is omf_qsgd_dev.h; here is what the encoder kernels build on it: their argument
 // record, the tail-safe quad load and payload store, a thread's row loads (fp32 arenas, and the 16-bit
-// arenas of omf_qsgd_h16.hip) with their scale and sum of squares, the Philox draws of a row group, the
+// arenas of omf_qsgd_h16.hip and omf_qsgd_bucket_h16.hip) with their scale and sum of squares, the Philox draws of a row group, the
 // quantise-and-store of a sub-chunk, the ticketed fold of a tensor's partials to its norm.  Every function is
 // __device__ __forceinline__ in an unnamed namespace, as the kernels are: each unit compiles its own
 // copy, and a kernel's name keeps its argument type.

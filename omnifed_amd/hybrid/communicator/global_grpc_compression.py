@@ -107,7 +107,8 @@ def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_rat
     max |v| in value_bits + 2 bits each, the quantisation error fed back through the residual.
     ``bucket_size`` (default None; needs ``scheme="qsgd"`` and no ``packed_wire``): ``QSGDBucketedCompression``
     layers, every bucket of that many consecutive elements (a power of two in [64, 4096]) quantised against
-    its own norm; fp32 tensors only.  ``bucket_packed`` (default off; needs ``bucket_size``):
+    its own norm; bf16 / fp16 tensors are encoded from a 16-bit arena as their exact fp32 upcast would be (no
+    fp32 copy, nothing rounded to the 16-bit format).  ``bucket_packed`` (default off; needs ``bucket_size``):
     ``QSGDBucketedPackedCompression`` layers, the bucketed update's codes on the bit-packed wire, packed inside
     the encode pass."""
     if not enabled:
@@ -818,16 +819,17 @@ def _encode_updates(updates, compressor, weight) -> list:
         from ..compression.qsgd import encode_bucketed, encode_groups
 
         levels = 2**compressor.s
-        if compressor.bucket_size is not None:  # one launch, one norm per bucket
-            plan, q, bn = encode_bucketed(flats, compressor.s, compressor.bucket_size, dev, compressor._next_call(),
-                                          alpha=_alpha(weight), key=compressor.philox_key(),
-                                          packed=compressor.bucket_packed)
-            got = qsgd_bucketed_layers_from_arena(plan, q, bn, [names[i] for i in comp_idx],
-                                                  [tuple(updates[names[i]].shape) for i in comp_idx], levels,
-                                                  compressor.bucket_size, packed=compressor.bucket_packed)
+        if compressor.bucket_size is not None:  # one launch per dtype (normally one), one norm per bucket
             groups = []
-            for i, L in zip(comp_idx, got):
-                layers[i] = L
+            for plan, q, bn, members in encode_bucketed(flats, compressor.s, compressor.bucket_size, dev,
+                                                        compressor._next_call(), alpha=_alpha(weight),
+                                                        key=compressor.philox_key(), packed=compressor.bucket_packed):
+                idx = [comp_idx[m] for m in members]
+                got = qsgd_bucketed_layers_from_arena(plan, q, bn, [names[i] for i in idx],
+                                                      [tuple(updates[names[i]].shape) for i in idx], levels,
+                                                      compressor.bucket_size, packed=compressor.bucket_packed)
+                for i, L in zip(idx, got):
+                    layers[i] = L
         else:
             groups = encode_groups(flats, compressor.s, dev, compressor.rng, compressor._next_call(),
                                    alpha=_alpha(weight), key=compressor.philox_key())

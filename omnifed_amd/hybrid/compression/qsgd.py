@@ -102,18 +102,26 @@ def _arena(flats: Sequence[torch.Tensor], dev: torch.device, plan) -> torch.Tens
 
 def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: int, dev: torch.device,
                     call_index: int = 0, alpha: float = 1.0, key: int = 0, packed: bool = False):
-    """Encode flat fp32 tensors with bucket norms in ONE launch (``Plan.qsgd_encode_bucketed``, on-device
-    draws): ``(plan, q_arena, bnorms_dev)``, tensor k's norms at ``plan.bucket_layout(bucket_size)[0][k]``.
-    ``packed``: ``Plan.qsgd_encode_bucketed_packed``, ``q_arena`` the packed arena (``qsgd_pack``'s layout).
-    A bf16 / fp16 tensor raises ``ValueError`` (fp32 arenas only)."""
-    for f in flats:
-        if f.dtype != torch.float32:
-            raise ValueError(f"bucketed QSGD encodes float32 tensors, not {f.dtype}")
-    plan = codec.Plan.get([int(f.numel()) for f in flats], device=dev)
-    x = gather_arena(flats, dev, plan)
-    encode = plan.qsgd_encode_bucketed_packed if packed else plan.qsgd_encode_bucketed
-    q, bn = encode(x, int(bit_width), bucket_size, alpha=alpha, seed=int(key) & (2**64 - 1), offset=call_index)
-    return plan, q, bn
+    """Encode flat fp32 / bf16 / fp16 tensors with bucket norms, ONE launch per dtype present (normally one;
+    ``Plan.qsgd_encode_bucketed``, on-device draws).  Returns ``[(plan, q_arena, bnorms_dev, members)]`` in
+    order of first appearance, as ``encode_groups``: ``members[k]`` is the index into ``flats`` of the plan's
+    tensor k, its norms at ``plan.bucket_layout(bucket_size)[0][k]``; key = ``key`` (+ the group's index),
+    stream offset = ``call_index``.  ``packed``: ``Plan.qsgd_encode_bucketed_packed``, ``q_arena`` the packed
+    arena (``qsgd_pack``'s layout).  bf16 / fp16 tensors are read from a 16-bit arena — the buffer they already
+    share at the plan's offsets (``shared_arena``), else one they are gathered into bit for bit — and encoded
+    as their exact fp32 upcast would be (omf_qsgd_encode_bucketed_h16): no fp32 copy at any size."""
+    members: Dict[torch.dtype, List[int]] = {}
+    for i, f in enumerate(flats):
+        value_format(f.dtype)
+        members.setdefault(f.dtype, []).append(i)
+    out = []
+    for g, (dt, idx) in enumerate(members.items()):
+        plan = codec.Plan.get([int(flats[i].numel()) for i in idx], device=dev)
+        x = gather_arena([flats[i] for i in idx], dev, plan, dt)
+        encode = plan.qsgd_encode_bucketed_packed if packed else plan.qsgd_encode_bucketed
+        q, bn = encode(x, int(bit_width), bucket_size, alpha=alpha, seed=(int(key) + g) & (2**64 - 1), offset=call_index)
+        out.append((plan, q, bn, idx))
+    return out
 
 
 def encode_groups(flats: Sequence[torch.Tensor], bit_width: int, dev: torch.device, rng: str = "philox",
@@ -225,8 +233,9 @@ class QSGDQuantCompression(Compression):
         self.device = torch.device(device)
         if rng not in ("philox", "mt19937"):
             raise ValueError(f"unknown rng={rng!r}; expected 'philox' or 'mt19937'")
-        # opt-in bucket norms (QSGDBucketedCompression layers): fp32 tensors, on-device draws, the int8 / int32
-        # levels; the reference has no buckets, so neither its stream (mt19937) nor the packed wire applies
+        # opt-in bucket norms (QSGDBucketedCompression layers): fp32 / bf16 / fp16 tensors, on-device draws, the
+        # int8 / int32 levels; the reference has no buckets, so neither its stream (mt19937) nor the packed wire
+        # applies
         self.bucket_size = None if bucket_size is None else int(bucket_size)
         if self.bucket_size is not None:
             codec.bucket_layout([], self.bucket_size)  # ValueError for a size that is not allowed
@@ -279,14 +288,14 @@ class QSGDQuantCompression(Compression):
         levels = 2**self.s
         width, _ = choose_qsgd_storage_width(levels)
         if self.bucket_size is not None:  # norm: the tensor's bucket norms, a 1-D fp32 CPU tensor
-            plan, q, bn = encode_bucketed(flats, self.s, self.bucket_size, dev, self._next_call(), alpha=alpha,
-                                          key=self.philox_key())
-            host = bn.cpu()  # synchronises the stream
-            boff, nb = plan.bucket_layout(self.bucket_size)
-            res: List[Tuple] = []
-            for o, n, b0, b1 in zip(plan.offsets, plan.sizes, boff, boff[1:] + [nb]):
-                mine = host[b0:b1].clone()
-                res.append((None, -1, -1, -1) if not bool(mine.any()) else (q[o:o + n], mine, width, levels))
+            res: List[Tuple] = [None] * len(flats)
+            for plan, q, bn, idx in encode_bucketed(flats, self.s, self.bucket_size, dev, self._next_call(),
+                                                    alpha=alpha, key=self.philox_key()):
+                host = bn.cpu()  # synchronises the stream
+                boff, nb = plan.bucket_layout(self.bucket_size)
+                for i, o, n, b0, b1 in zip(idx, plan.offsets, plan.sizes, boff, boff[1:] + [nb]):
+                    mine = host[b0:b1].clone()
+                    res[i] = (None, -1, -1, -1) if not bool(mine.any()) else (q[o:o + n], mine, width, levels)
             return res
         groups = encode_groups(flats, self.s, dev, self.rng, self._next_call(), alpha=alpha, key=self.philox_key())
         out: List[Tuple] = [None] * len(flats)
