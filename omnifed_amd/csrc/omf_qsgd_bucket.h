@@ -28,6 +28,8 @@
 //   4. waves          d >= 512: the groups of 64 lanes are added as w ^ 1 (d = 512: (g0 + g1)), then w ^ 2
 //                     (d >= 1024: ((g0 + g1) + (g2 + g3)));
 //   5. norm_b = sqrtf(sum), correctly rounded.
+// Plain IEEE fp32 with gradual underflow (the build keeps denormals).  oracle/qsgd_bucket.py is the executable form
+// of steps 1-5; tests/test_gpu_qsgd_bucket_matrix.py holds every unit's norm bits to it.
 #pragma once
 
 #include <stddef.h>

@@ -30,3 +30,4 @@ from .topk import (  # noqa: F401
     topk_sparse,
 )
 from .aggregate import ps_aggregate, layerwise_decompress  # noqa: F401
+from .qsgd_bucket import bucket_norms, decode_bucketed, encode_bucketed  # noqa: F401

@@ -18,7 +18,7 @@ from omnifed_amd.hybrid.compression.qsgd import encode_bucketed
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (64, 256, 1024, 4096)
+SIZES = codec.BUCKET_SIZES
 FORMATS = (torch.bfloat16, torch.float16)
 SEED, OFF, GUARD = 0xB16, 3, 64
 

@@ -23,7 +23,7 @@ from oracle import bitpack
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (64, 256, 1024, 4096)
+SIZES = codec.BUCKET_SIZES
 SEED, OFF = 0xB0C, 3
 GUARD = 64
 CANARY = 0x5A5A5A5A
@@ -167,7 +167,7 @@ def test_packed_bucketed_decode_of_foreign_messages(gpu, arenas, d, L, accumulat
 @pytest.mark.parametrize("divisor", (None, 7.0))
 @pytest.mark.parametrize("init", (False, True))
 @pytest.mark.parametrize("K", (1, 3, 9))
-@pytest.mark.parametrize("d,L", ((64, 16), (1024, 256), (4096, 100)))
+@pytest.mark.parametrize("d,L", ((64, 16), (1024, 256), (4096, 100), (128, 256), (512, 100), (2048, 16)))
 def test_packed_bucketed_decode_sum_is_the_sequential_sum(gpu, arenas, d, L, K, init, divisor):
     plan, _, mask, bidx = arenas[d]
     msgs = [_message(plan, d, gpu, L, 20 + k) for k in range(K)]

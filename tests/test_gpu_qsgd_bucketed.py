@@ -21,7 +21,7 @@ from omnifed_amd.ps import DeviceAggregator
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (64, 256, 1024, 4096)
+SIZES = codec.BUCKET_SIZES
 SEED, OFF = 0xB0C, 3
 GUARD = 64
 CANARY = 3e4
@@ -175,7 +175,8 @@ def test_bucketed_decode_of_foreign_messages(gpu, arenas, d, width, L, accumulat
 @pytest.mark.parametrize("divisor", (None, 7.0))
 @pytest.mark.parametrize("init", (False, True))
 @pytest.mark.parametrize("K", (1, 3, 9))
-@pytest.mark.parametrize("d,width,L", ((64, 8, 16), (1024, 32, 256), (4096, 8, 100)))
+@pytest.mark.parametrize("d,width,L", ((64, 8, 16), (1024, 32, 256), (4096, 8, 100), (128, 32, 256), (512, 8, 100),
+                                       (2048, 8, 16)))
 def test_bucketed_decode_sum_is_the_sequential_sum(gpu, arenas, d, width, L, K, init, divisor):
     plan, x, mask, bidx = arenas[d]
     msgs = [_message(plan, d, gpu, width, L, 20 + k) for k in range(K)]
