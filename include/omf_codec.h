@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 121
+#define OMF_ABI_VERSION 122
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -135,7 +135,8 @@ int32_t omf_plan_encode_strategy(const omf_plan* plan);
  * 6 the 16-bit-arena encoder (omf_qsgd_encode_h16), 7 the bucketed encoder (omf_qsgd_encode_bucketed), 8 the
  * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed), 9 the bucketed PS step's fused launch
  * (omf_ps_sum_encode_bucketed), 10 / 11 the bucketed encoders of a 16-bit arena (omf_qsgd_encode_bucketed_h16 /
- * omf_qsgd_encode_bucketed_packed_h16); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * omf_qsgd_encode_bucketed_packed_h16), 12 / 13 the max-scaled bucketed encoder without / with its rotation
+ * (omf_qsgd_encode_bucketed_max); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -328,6 +329,51 @@ int omf_qsgd_decode_bucketed(omf_plan* plan, const void* q, int32_t width, int32
 int omf_qsgd_decode_sum_bucketed(omf_plan* plan, const void* const* q, const float* const* bnorm, int32_t nclients,
                                  int32_t width, int32_t levels, int64_t bucket_size, float* y_out, int32_t init,
                                  float divisor, void* stream);
+
+/*
+ * Opt-in max-scaled buckets, and a randomised Hadamard rotation of full buckets before quantising (Suresh et al.,
+ * 2017; NOT reference-compatible).  The buckets, their arena, the draws, the payload and the decode rule
+ * fl32(fl32(scale * q) / fl32(levels)) are omf_qsgd_encode_bucketed's; what changes is the bucket's scale and the
+ * domain the levels are taken in (omnifed_amd/csrc/omf_qsgd_bucket_rot.h holds the rules):
+ *   scale      max |z_i| over the bucket, exact and order-free (0 gives zero levels);
+ *   z          xs = fl32(x * alpha) itself, or with rotate != 0, for every FULL bucket, H_d (sigma . xs): the
+ *              unnormalised Walsh-Hadamard transform in fp32 adds of a fixed order, sigma_j = +-1 a stateless
+ *              function of (rot_seed, tensor, element).  A tensor's short last bucket is never rotated.
+ * Without rotation the payload and scale arena are read by omf_qsgd_decode_bucketed / omf_qsgd_decode_sum_bucketed /
+ * omf_ps_sum_encode_bucketed unchanged.  With rotation the receiver needs bucket_size and rot_seed:
+ *   omf_qsgd_encode_bucketed_max      omf_qsgd_encode_bucketed's arguments, rotate and rot_seed; one launch, x read
+ *                                     once.  bnorm_in replaces the computed scales.
+ *   omf_qsgd_scales_bucketed_max      the scales alone: the same bits.
+ *   omf_qsgd_rotate_bucketed          the transform alone over an fp32 arena: y = H_d (sigma . x) per full bucket
+ *                                     (inverse == 0) or y = sigma . (H_d x) / d (inverse != 0); short last buckets
+ *                                     are copied, padding is not written.  y_out may be x.
+ *   omf_qsgd_decode_bucketed_rot      omf_qsgd_decode_bucketed of a rotated payload.
+ *   omf_qsgd_decode_sum_bucketed_rot  omf_qsgd_decode_sum_bucketed of clients that share bucket_size and rot_seed: the
+ *                                     clients' decoded levels are summed in array order in the rotated domain, the
+ *                                     sum is transformed back once, then y = init ? y + sum : sum, then / divisor.
+ *                                     (With init != 0 and more than 8 clients each group of 8 is transformed back
+ *                                     and added to y in turn.)  Padding as omf_qsgd_decode_sum_bucketed.
+ *   omf_qsgd_rotation_signs           host only: signs_out[i] = sigma (+1 / -1) of element begin + i of a tensor.
+ * tensor_keyed != 0: sigma is keyed by (rot_seed, the tensor's index in the plan, element), as omf_qsgd_rotation_signs
+ * gives it; 0: by (rot_seed, element) alone, every tensor as tensor 0 — what a wire uses whose receiver numbers the
+ * tensors of a message differently from the sender (a layer then needs only bucket_size and rot_seed).
+ * fp32 arenas and the int8 / int32 wire only.  Errors as omf_qsgd_encode_bucketed / omf_qsgd_decode_sum_bucketed.
+ */
+int omf_qsgd_encode_bucketed_max(omf_plan* plan, const float* x, float alpha, int32_t bit_width, int64_t bucket_size,
+                                 const float* u, uint64_t seed, uint64_t offset, const float* bnorm_in, void* q_out,
+                                 float* bnorm_out, int32_t rotate, uint32_t rot_seed, int32_t tensor_keyed,
+                                 void* stream);
+int omf_qsgd_scales_bucketed_max(omf_plan* plan, const float* x, float alpha, int64_t bucket_size, int32_t rotate,
+                                 uint32_t rot_seed, int32_t tensor_keyed, float* bnorm_out, void* stream);
+int omf_qsgd_rotate_bucketed(omf_plan* plan, const float* x, int64_t bucket_size, uint32_t rot_seed, int32_t tensor_keyed,
+                             int32_t inverse, float* y_out, void* stream);
+int omf_qsgd_decode_bucketed_rot(omf_plan* plan, const void* q, int32_t width, int32_t levels, int64_t bucket_size,
+                                 uint32_t rot_seed, int32_t tensor_keyed, const float* bnorm, float* y_out,
+                                 int32_t accumulate, void* stream);
+int omf_qsgd_decode_sum_bucketed_rot(omf_plan* plan, const void* const* q, const float* const* bnorm, int32_t nclients,
+                                     int32_t width, int32_t levels, int64_t bucket_size, uint32_t rot_seed, int32_t tensor_keyed,
+                                     float* y_out, int32_t init, float divisor, void* stream);
+int omf_qsgd_rotation_signs(uint32_t rot_seed, int32_t tensor, int64_t begin, int64_t count, int8_t* signs_out);
 
 /*
  * Opt-in bit-packed QSGD wire (NOT reference-compatible, a new

@@ -77,6 +77,17 @@ SIGNATURES = {
     "omf_qsgd_decode_bucketed": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i64, _c_p, _c_p, _c_i32, _c_p]),
     "omf_qsgd_decode_sum_bucketed": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32,
                                                     _c_i32, _c_i64, _c_p, _c_i32, _c_f32, _c_p]),
+    "omf_qsgd_encode_bucketed_max": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_i32, _c_i64, _c_p, _c_u64, _c_u64, _c_p,
+                                                    _c_p, _c_p, _c_i32, ctypes.c_uint32, _c_i32, _c_p]),
+    "omf_qsgd_scales_bucketed_max": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_i64, _c_i32, ctypes.c_uint32, _c_i32, _c_p,
+                                                    _c_p]),
+    "omf_qsgd_rotate_bucketed": (ctypes.c_int, [_c_p, _c_p, _c_i64, ctypes.c_uint32, _c_i32, _c_i32, _c_p, _c_p]),
+    "omf_qsgd_decode_bucketed_rot": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i64, ctypes.c_uint32, _c_i32, _c_p,
+                                                    _c_p, _c_i32, _c_p]),
+    "omf_qsgd_decode_sum_bucketed_rot": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32,
+                                                        _c_i32, _c_i32, _c_i64, ctypes.c_uint32, _c_i32, _c_p, _c_i32,
+                                                        _c_f32, _c_p]),
+    "omf_qsgd_rotation_signs": (ctypes.c_int, [ctypes.c_uint32, _c_i32, _c_i64, _c_i64, _c_p]),
     "omf_plan_set_bucket_rows": (ctypes.c_int, [_c_p, _c_i32, _c_i32]),
     "omf_qsgd_encode_bucketed_packed": (ctypes.c_int, [_c_p, _c_p, _c_f32, _c_i32, _c_i64, _c_p, _c_u64, _c_u64, _c_p,
                                                        _c_p, _c_p, _c_p]),
@@ -133,7 +144,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 121 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 122 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

@@ -138,6 +138,22 @@ def _h16_format(x: torch.Tensor, value_format: int) -> int:
     return fmt
 
 
+def _rotation_seed(seed) -> int:
+    """A rotation seed of the max-scaled bucketed wire: an int in [0, 2^31) (it travels in an int32 ``param_shape``)."""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 31:
+        raise ValueError(f"rotation_seed={seed!r}: expected an int in [0, 2^31)")
+    return seed
+
+
+def rotation_signs(rotation_seed: int, tensor: int, begin: int, count: int) -> torch.Tensor:
+    """The rotation's signs (omf_qsgd_rotation_signs, host only): an int8 tensor of +1 / -1 for elements
+    ``begin .. begin + count - 1`` of the plan's tensor number ``tensor``."""
+    out = torch.empty(int(count), dtype=torch.int8)
+    check(lib().omf_qsgd_rotation_signs(_rotation_seed(rotation_seed), int(tensor), int(begin), int(count),
+                                        ctypes.c_void_p(out.data_ptr())), "omf_qsgd_rotation_signs")
+    return out
+
+
 def _bucket_format(x) -> int:
     """The value format of a bucketed encode's arena: 0 for fp32, the 16-bit arena's own for bf16 / fp16; any other
     dtype raises ``ValueError``."""
@@ -295,11 +311,12 @@ class Plan:
         """The encoder the latest encode launched (omf_plan_last_encoder): one of STRATEGIES,
         "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms),
         "bucketed_packed" (bucket norms, codes packed in the pass), "bucketed_ps" (the bucketed PS step's fused
-        launch), "bucketed_h16" / "bucketed_packed_h16" (the bucketed encoders of a bf16 / fp16 arena) or "none"."""
+        launch), "bucketed_h16" / "bucketed_packed_h16" (the bucketed encoders of a bf16 / fp16 arena), "bucketed_max" /
+        "bucketed_max_rot" (max-scaled buckets without / with the Hadamard rotation) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
         return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {
             5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed", 9: "bucketed_ps",
-            10: "bucketed_h16", 11: "bucketed_packed_h16"}.get(code, "none")
+            10: "bucketed_h16", 11: "bucketed_packed_h16", 12: "bucketed_max", 13: "bucketed_max_rot"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -713,6 +730,142 @@ class Plan:
         results."""
         with self._lock:
             check(lib().omf_plan_set_bucket_rows(self._h, int(rows), 1 if static_d else 0), "omf_plan_set_bucket_rows")
+
+    # ------------------------------------------------------------ max-scaled buckets, Hadamard rotation (opt-in)
+    def qsgd_encode_bucketed_max(self, x: torch.Tensor, bit_width: int, bucket_size: int, rotate: bool = False,
+                                 rotation_seed: int = 0, tensor_keyed: bool = True, q_out: Optional[torch.Tensor] = None,
+                                 bnorm_out: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                                 u: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+                                 bnorm_in: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        """omf_qsgd_encode_bucketed_max: ``qsgd_encode_bucketed`` with every bucket scaled by its max |z| instead of
+        its L2 norm, z the scaled values or, with ``rotate``, the randomised Hadamard transform of every full bucket
+        (csrc/omf_qsgd_bucket_rot.h).  ``tensor_keyed=False`` keys the signs by the element alone (every tensor as
+        tensor 0: the hybrid wire's choice), on this and the four methods below.  Returns ``(q, scales)``; fp32 arenas
+        only."""
+        _, nb = self.bucket_layout(bucket_size)
+        s = int(bit_width)
+        if not 0 <= s <= 30:
+            raise ValueError("bit_width must be in [0, 30]")
+        rs = _rotation_seed(rotation_seed)
+        width = storage_width(2 ** s)
+        qdt = torch.int8 if width == 8 else torch.int32
+        dev = self.device
+        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        if q_out is None:
+            q_out = torch.empty(self.payload_elems(width), dtype=qdt, device=dev)
+        _need(q_out, "q_out", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        if u is not None:
+            _need(u, "u", torch.float32, dev, self.arena_end, 16)
+        if bnorm_in is not None:
+            _need(bnorm_in, "bnorm_in", torch.float32, dev, nb, 4)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_encode_bucketed_max(
+                self._h, _ptr(x), float(alpha), s, int(bucket_size), _ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(bnorm_in), _ptr(q_out), _ptr(bnorm_out), 1 if rotate else 0, rs,
+                1 if tensor_keyed else 0, ctypes.c_void_p(st)), "omf_qsgd_encode_bucketed_max")
+        return q_out, bnorm_out
+
+    def qsgd_scales_bucketed_max(self, x: torch.Tensor, bucket_size: int, rotate: bool = False, rotation_seed: int = 0,
+                                 tensor_keyed: bool = True, alpha: float = 1.0, bnorm_out: Optional[torch.Tensor] = None,
+                                 stream: Optional[int] = None) -> torch.Tensor:
+        """The scales alone (omf_qsgd_scales_bucketed_max): the bits ``qsgd_encode_bucketed_max`` writes."""
+        _, nb = self.bucket_layout(bucket_size)
+        _need(x, "x", torch.float32, self.device, self.arena_end, 16)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        st = stream if stream is not None else _stream(self.device)
+        with self._lock:
+            check(lib().omf_qsgd_scales_bucketed_max(self._h, _ptr(x), float(alpha), int(bucket_size), 1 if rotate else 0,
+                                                     _rotation_seed(rotation_seed), 1 if tensor_keyed else 0,
+                                                     _ptr(bnorm_out), ctypes.c_void_p(st)),
+                  "omf_qsgd_scales_bucketed_max")
+        return bnorm_out
+
+    def qsgd_rotate_bucketed(self, x: torch.Tensor, bucket_size: int, rotation_seed: int = 0, inverse: bool = False,
+                             y_out: Optional[torch.Tensor] = None, tensor_keyed: bool = True, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_rotate_bucketed: the transform alone over an fp32 arena — ``H_d (sigma . x)`` per full bucket, or
+        with ``inverse`` ``sigma . (H_d x) / d``; short last buckets are copied.  ``y_out`` may be ``x``; a new
+        ``y_out`` starts from zeros (the padding is not written)."""
+        self.bucket_layout(bucket_size)
+        dev = self.device
+        _need(x, "x", torch.float32, dev, self.arena_end, 16)
+        if y_out is None:
+            y_out = torch.zeros(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_rotate_bucketed(self._h, _ptr(x), int(bucket_size), _rotation_seed(rotation_seed),
+                                                 1 if tensor_keyed else 0, 1 if inverse else 0, _ptr(y_out), ctypes.c_void_p(st)),
+                  "omf_qsgd_rotate_bucketed")
+        return y_out
+
+    def qsgd_decode_bucketed_rot(self, q: torch.Tensor, width: int, levels: int, bucket_size: int, rotation_seed: int,
+                                 bnorm: torch.Tensor, y_out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                                 tensor_keyed: bool = True, stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_bucketed_rot: ``qsgd_decode_bucketed`` of a rotated payload."""
+        width, levels = int(width), int(levels)
+        if width not in (8, 32):
+            raise ValueError(f"unsupported width={width}")
+        if levels <= 0:
+            raise ValueError(f"invalid level={levels}")
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        _need(q, "q", torch.int8 if width == 8 else torch.int32, dev, self.arena_end, 4 if width == 8 else 16)
+        _need(bnorm, "bnorm", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_decode_bucketed_rot(self._h, _ptr(q), width, levels, int(bucket_size),
+                                                     _rotation_seed(rotation_seed), 1 if tensor_keyed else 0,
+                                                     _ptr(bnorm), _ptr(y_out), 1 if accumulate else 0, ctypes.c_void_p(st)),
+                  "omf_qsgd_decode_bucketed_rot")
+        return y_out
+
+    def qsgd_decode_sum_bucketed_rot(self, qs: Sequence[torch.Tensor], width: int, levels: int, bucket_size: int,
+                                     rotation_seed: int, bnorms: Sequence[torch.Tensor],
+                                     y_out: Optional[torch.Tensor] = None, init: bool = False,
+                                     divisor: Optional[float] = None, tensor_keyed: bool = True,
+                                     stream: Optional[int] = None) -> torch.Tensor:
+        """omf_qsgd_decode_sum_bucketed_rot: ``qsgd_decode_sum_bucketed`` over rotated payloads that share
+        ``bucket_size`` and ``rotation_seed``: summed in the rotated domain, transformed back once."""
+        width, levels = int(width), int(levels)
+        if width not in (8, 32):
+            raise ValueError(f"unsupported width={width}")
+        if levels <= 0:
+            raise ValueError(f"invalid level={levels}")
+        qs, bnorms = list(qs), list(bnorms)
+        if not qs or len(qs) != len(bnorms):
+            raise ValueError(f"qsgd_decode_sum_bucketed_rot needs one scale arena per payload and at least one "
+                             f"({len(qs)}, {len(bnorms)})")
+        _, nb = self.bucket_layout(bucket_size)
+        dev = self.device
+        qdt = torch.int8 if width == 8 else torch.int32
+        for k, (q, nm) in enumerate(zip(qs, bnorms)):
+            _need(q, f"qs[{k}]", qdt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+            _need(nm, f"bnorms[{k}]", torch.float32, dev, nb, 4)
+        if y_out is None:
+            if init:
+                raise ValueError("init=True needs y_out")
+            y_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(y_out, "y_out", torch.float32, dev, self.arena_end, 16)
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        n = len(qs)
+        qp = (ctypes.c_void_p * n)(*[q.data_ptr() for q in qs])
+        npp = (ctypes.c_void_p * n)(*[nm.data_ptr() for nm in bnorms])
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:
+            check(lib().omf_qsgd_decode_sum_bucketed_rot(self._h, qp, npp, n, width, levels, int(bucket_size),
+                                                         _rotation_seed(rotation_seed), 1 if tensor_keyed else 0,
+                                                         _ptr(y_out), 1 if init else 0, d,
+                                                         ctypes.c_void_p(st)), "omf_qsgd_decode_sum_bucketed_rot")
+        return y_out
 
     # ------------------------------------------------------------ bucket norms on the bit-packed wire (opt-in)
     def qsgd_encode_bucketed_packed(self, x: torch.Tensor, bit_width: int, bucket_size: int,

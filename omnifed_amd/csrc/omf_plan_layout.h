@@ -195,6 +195,8 @@ enum Encoder : int32_t {
   kEncBucketedPs = 9,   // the bucketed PS step's fused launch (omf_qsgd_bucket_ps.hip): the entry point's
   kEncBucketedH16 = 10,        // bucket norms from a 16-bit arena (omf_qsgd_bucket_h16.hip): the entry point's
   kEncBucketedPackedH16 = 11,  // the same on the bit-packed wire (omf_qsgd_bucket_h16.hip): the entry point's
+  kEncBucketedMax = 12,        // max-scaled buckets (omf_qsgd_bucket_rot.hip): the entry point's
+  kEncBucketedMaxRot = 13,     // the same with the Hadamard rotation (omf_qsgd_bucket_rot.hip): the entry point's
 };
 
 struct Call {

@@ -67,6 +67,9 @@ inline int64_t offsets(const int64_t* sizes, int32_t nt, int logd, int64_t* boff
 }  // namespace omf
 
 #ifdef __HIPCC__
+#include <string>
+#include <vector>
+
 #include "omf_common.h"
 #include "omf_plan.h"
 #include "omf_qsgd_dec.h"
@@ -149,20 +152,45 @@ using namespace omf;
 constexpr const char* kBucketMisaligned = "misaligned buffer (fp32/int32 need 16 B, int8 needs 4 B alignment)";
 constexpr const char* kBucketBadSize = "bucket_size must be a power of two in [64, 4096]";
 
+// The caller's norms (or scales) of a block's V rows: norm[k] of the bucket that holds this thread's quad of row k,
+// 0 for a quad past `end`.
+template <bool FULL, int V>
+__device__ __forceinline__ void bucket_norms_in(const float* __restrict__ norm_in, int64_t b, int64_t end, int64_t tbegin,
+                                                int64_t nbase, int logd, float (&norm)[V]) {
+  const int tid = (int)threadIdx.x;
+  const int64_t rel = (b - tbegin) + 4 * tid;  // this thread's row 0, from the tensor's begin
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    const bool live = FULL || b + 4 * ((int64_t)k * kThreads + tid) < end;
+    norm[k] = live ? norm_in[nbase + ((rel + 1024 * k) >> logd)] : 0.0f;
+  }
+}
+
+// The bucket's first lane (of its first row) stores the bucket's norm (or scale).
+template <bool FULL, int V>
+__device__ __forceinline__ void bucket_norms_store(float* __restrict__ norm_out, int64_t b, int64_t end, int64_t tbegin,
+                                                   int64_t nbase, int logd, const float (&norm)[V]) {
+  const int tid = (int)threadIdx.x;
+  const int64_t rel = (b - tbegin) + 4 * tid;
+  const int lane_mask = logd <= 10 ? (1 << (logd - 2)) - 1 : kThreads - 1;
+  const int row_mask = logd <= 10 ? 0 : (1 << (logd - 10)) - 1;
+  if ((tid & lane_mask) == 0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (k & row_mask) continue;
+      if (FULL || b + 4 * ((int64_t)k * kThreads + tid) < end) norm_out[nbase + ((rel + 1024 * k) >> logd)] = norm[k];
+    }
+  }
+}
+
 // The norm half of a block's front: v holds the block's V rows of values (+0 at elements past `end`); norm[k]
 // becomes the norm of the bucket that holds this thread's quad of row k — computed (bucket_sums) or the
 // caller's — and the bucket's first lane (of its first row) stores it.  Called by the whole workgroup.
 template <bool FULL, int V>
 __device__ __forceinline__ void bucket_norms(const EncArgs& a, int64_t b, int64_t end, int64_t tbegin, int64_t nbase,
                                              int logd, float (*xch)[kWaves], const float4 (&v)[V], float (&norm)[V]) {
-  const int tid = (int)threadIdx.x;
-  const int64_t rel = (b - tbegin) + 4 * tid;  // this thread's row 0, from the tensor's begin
   if (a.norm_in) {  // the caller's norms (uniform branch)
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const bool live = FULL || b + 4 * ((int64_t)k * kThreads + tid) < end;
-      norm[k] = live ? a.norm_in[nbase + ((rel + 1024 * k) >> logd)] : 0.0f;
-    }
+    bucket_norms_in<FULL, V>(a.norm_in, b, end, tbegin, nbase, logd, norm);
   } else {
 #pragma unroll
     for (int k = 0; k < V; ++k) norm[k] = sq4(v[k], 0.0f);
@@ -170,16 +198,7 @@ __device__ __forceinline__ void bucket_norms(const EncArgs& a, int64_t b, int64_
 #pragma unroll
     for (int k = 0; k < V; ++k) norm[k] = sqrtf(norm[k]);
   }
-  // the bucket's first lane (of its first row) stores the norm
-  const int lane_mask = logd <= 10 ? (1 << (logd - 2)) - 1 : kThreads - 1;
-  const int row_mask = logd <= 10 ? 0 : (1 << (logd - 10)) - 1;
-  if ((tid & lane_mask) == 0) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if (k & row_mask) continue;
-      if (FULL || b + 4 * ((int64_t)k * kThreads + tid) < end) a.norm_out[nbase + ((rel + 1024 * k) >> logd)] = norm[k];
-    }
-  }
+  bucket_norms_store<FULL, V>(a.norm_out, b, end, tbegin, nbase, logd, norm);
 }
 
 // The front half of one block [b, end) of V rows of a tensor (begins at tbegin; its norms at nbase of the
@@ -301,6 +320,20 @@ __device__ __forceinline__ void pack_rows(const float4 (&v)[kPackRows], const fl
   }
 }
 
+// A payload quad (WIDTH 1: its dword of int8 levels in raw[0]; 4: raw[0..3]) decoded against its bucket's norm
+// (omf_qsgd_bucketed.hip's sums, omf_qsgd_bucket_rot.hip's).
+template <int WIDTH, bool POW2>
+__device__ __forceinline__ void dec_quad(const int32_t* raw, float norm, float levels, float inv_levels, float (&yv)[4]) {
+  int32_t qi[4];
+  if (WIDTH == 1) {
+    qsgd_split_i8(raw[0], qi);
+  } else {
+    qi[0] = raw[0]; qi[1] = raw[1]; qi[2] = raw[2]; qi[3] = raw[3];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) yv[c] = qsgd_dec_elem<POW2>(norm, qi[c], levels, inv_levels);
+}
+
 constexpr int kBucketSumMax = 8;  // clients per launch; the calls chain groups (sum_group, omf_qsgd_dec.h)
 template <int N>
 struct BSumArgs {  // SumArgs of omf_qsgd_recv.hip; q[k] is client k's payload (levels, or the packed words),
@@ -311,6 +344,33 @@ struct BSumArgs {  // SumArgs of omf_qsgd_recv.hip; q[k] is client k's payload (
   float divisor, pad_div;
   int32_t init, fill;
 };
+
+// What the receive calls of the int8 / int32 bucketed wire check before anything is launched (`who`: the entry
+// point, `plain`: its one-client form); *logd: log2 of the bucket size.
+inline int bucket_sum_checks(const omf_plan* p, const void* const* q, const float* const* bnorm, int32_t nclients,
+                             int32_t width, int32_t levels, int64_t d, const float* y, bool plain, const std::string& who,
+                             int* logd_out) {
+  if (!p) return fail(OMF_EINVAL, "plan is NULL");
+  const int logd = bucket::log2_size(d);
+  if (logd < 0) return fail(OMF_EINVAL, kBucketBadSize);
+  if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
+  if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
+  if (nclients < 1) return fail(OMF_EINVAL, who + ": nclients must be >= 1");
+  if (!q || !bnorm || !y) return fail(OMF_EINVAL, "q, bnorm and y_out must be non-NULL");
+  if (!aligned(y, 16)) return fail(OMF_EINVAL, kBucketMisaligned);
+  const int64_t nb = bucket::offsets(p->sizes.data(), p->nt, logd, nullptr);
+  const size_t ybytes = (size_t)p->arena_end * 4;
+  const size_t qbytes = width == 8 ? (size_t)((p->arena_end + 3) & ~(int64_t)3) : (size_t)p->arena_end * 4;
+  for (int32_t k = 0; k < nclients; ++k) {
+    if (!q[k] || !bnorm[k]) return fail(OMF_EINVAL, who + (plain ? ": q and bnorm must be non-NULL" : ": a NULL entry in q or bnorm"));
+    if (!aligned(q[k], width == 8 ? 4 : 16) || !aligned(bnorm[k], 4)) return fail(OMF_EINVAL, kBucketMisaligned);
+    if (overlaps(y, ybytes, q[k], qbytes) || overlaps(y, ybytes, bnorm[k], (size_t)nb * 4))
+      return fail(OMF_EINVAL, who + ": y_out overlaps a payload or norm buffer");
+  }
+  if (!p->d_block) return fail(OMF_EHIP, "the plan's tables are not on the device (an earlier upload failed)");
+  *logd_out = logd;
+  return OMF_OK;
+}
 
 // The plan's tables of bucket size 2^logd: boff on the device, nb on the host.  Built and uploaded at the
 // first call at that size (synchronous), kept for the plan's life (at most bucket::kSizes of them): no later

@@ -101,18 +101,6 @@ BucketKernel encode_kernel_static(int logd, bool w, bool u) {
 
 // ---------------------------------------------------------------- decode and sum
 
-template <int WIDTH, bool POW2>
-__device__ __forceinline__ void dec_quad(const int32_t* raw, float norm, float levels, float inv_levels, float (&yv)[4]) {
-  int32_t qi[4];
-  if (WIDTH == 1) {
-    qsgd_split_i8(raw[0], qi);
-  } else {
-    qi[0] = raw[0]; qi[1] = raw[1]; qi[2] = raw[2]; qi[3] = raw[3];
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) yv[c] = qsgd_dec_elem<POW2>(norm, qi[c], levels, inv_levels);
-}
-
 constexpr int64_t kSumBlk = (int64_t)kThreads * 4;  // elements per workgroup
 static_assert(kDecBlk % kSumBlk == 0, "whole sum blocks per binfo table block");
 
@@ -297,24 +285,8 @@ void launch_sum(const BSumCall& c) {
 int sum_bucketed(omf_plan* p, const void* const* q, const float* const* bnorm, int32_t nclients, int32_t width,
                  int32_t levels, int64_t d, float* y, int32_t init, float divisor, bool plain, void* stream) {
   const std::string who = plain ? "omf_qsgd_decode_bucketed" : "omf_qsgd_decode_sum_bucketed";
-  if (!p) return fail(OMF_EINVAL, "plan is NULL");
-  const int logd = bucket::log2_size(d);
-  if (logd < 0) return fail(OMF_EINVAL, kBucketBadSize);
-  if (width != 8 && width != 32) return fail(OMF_EINVAL, "width must be 8 or 32");
-  if (levels <= 0) return fail(OMF_EINVAL, "levels must be > 0");
-  if (nclients < 1) return fail(OMF_EINVAL, who + ": nclients must be >= 1");
-  if (!q || !bnorm || !y) return fail(OMF_EINVAL, "q, bnorm and y_out must be non-NULL");
-  if (!aligned(y, 16)) return fail(OMF_EINVAL, kBucketMisaligned);
-  const int64_t nb = bucket::offsets(p->sizes.data(), p->nt, logd, nullptr);
-  const size_t ybytes = (size_t)p->arena_end * 4;
-  const size_t qbytes = width == 8 ? (size_t)((p->arena_end + 3) & ~(int64_t)3) : (size_t)p->arena_end * 4;
-  for (int32_t k = 0; k < nclients; ++k) {
-    if (!q[k] || !bnorm[k]) return fail(OMF_EINVAL, who + (plain ? ": q and bnorm must be non-NULL" : ": a NULL entry in q or bnorm"));
-    if (!aligned(q[k], width == 8 ? 4 : 16) || !aligned(bnorm[k], 4)) return fail(OMF_EINVAL, kBucketMisaligned);
-    if (overlaps(y, ybytes, q[k], qbytes) || overlaps(y, ybytes, bnorm[k], (size_t)nb * 4))
-      return fail(OMF_EINVAL, who + ": y_out overlaps a payload or norm buffer");
-  }
-  if (!p->d_block) return fail(OMF_EHIP, "the plan's tables are not on the device (an earlier upload failed)");
+  int logd = 0;
+  if (int r = bucket_sum_checks(p, q, bnorm, nclients, width, levels, d, y, plain, who, &logd)) return r;
   DeviceGuard g(p->device);
   if (!g.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   const LevelScale lv(levels);

@@ -39,6 +39,7 @@ from ..compression.qsgd import (
     QSGD_BUCKETED_PACKED_COMPRESSION_NAME,
     QSGD_COMPRESSION_NAME,
     QSGD_PACKED_COMPRESSION_NAME,
+    QSGD_ROTATED_BUCKETED_COMPRESSION_NAME,
     QSGDQuantCompression,
     choose_qsgd_storage_width,
     should_compress_tensor,
@@ -53,10 +54,11 @@ GlobalHybridCompressor = Union[TopKCompression, QSGDQuantCompression]
 _QSGD_NUMPY_DTYPES = {8: np.int8, 32: np.int32}
 _QSGD_TORCH_DTYPES = {8: torch.int8, 32: torch.int32}
 _QSGD_TYPES = (QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME,
-               QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+               QSGD_BUCKETED_PACKED_COMPRESSION_NAME, QSGD_ROTATED_BUCKETED_COMPRESSION_NAME)
 # the wires whose values_data is a stream of b-bit codes / whose meta_tensor holds bucket norms
 _QSGD_CODE_TYPES = (QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
-_QSGD_BUCKET_TYPES = (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+_QSGD_BUCKET_TYPES = (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME,
+                      QSGD_ROTATED_BUCKETED_COMPRESSION_NAME)
 _TOPK_TYPES = (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
 # the two types that share the packed index wire: a message or an update may mix them
 _TOPK_PACKED_TYPES = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
@@ -98,7 +100,8 @@ def compression_mode_name(compressor: Optional[GlobalHybridCompressor]) -> str:
 def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_ratio: float = 0.01,
                             bit_width: int = 8, device="cpu", packed_wire: bool = False,
                             value_bits=None, bucket_size=None,
-                            bucket_packed: bool = False) -> Optional[GlobalHybridCompressor]:
+                            bucket_packed: bool = False, bucket_norm: str = "l2", rotate: bool = False,
+                            rotation_seed: int = 0) -> Optional[GlobalHybridCompressor]:
     """global_grpc_compression.py:35-52.  ``packed_wire`` (default off): the scheme's opt-in bit-packed
     wire — ``QSGDBitPackedCompression`` (the levels in ceil(log2(2L + 1)) bits) or
     ``TopKBitPackedCompression`` (the indices in max(1, bit_length(n - 1)) bits); neither is readable
@@ -110,13 +113,18 @@ def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_rat
     its own norm; bf16 / fp16 tensors are encoded from a 16-bit arena as their exact fp32 upcast would be (no
     fp32 copy, nothing rounded to the 16-bit format).  ``bucket_packed`` (default off; needs ``bucket_size``):
     ``QSGDBucketedPackedCompression`` layers, the bucketed update's codes on the bit-packed wire, packed inside
-    the encode pass."""
+    the encode pass.  ``bucket_norm`` (default "l2"; "max" needs ``bucket_size``, no ``bucket_packed`` and fp32
+    tensors): every bucket scaled by its max |v| instead of its L2 norm; the layers stay ``QSGDBucketedCompression``.
+    ``rotate`` (default off; needs ``bucket_norm="max"``) with ``rotation_seed`` (an int in [0, 2^31)): full buckets
+    are rotated by a randomised Hadamard transform before quantising; ``QSGDRotatedBucketedCompression`` layers."""
     if not enabled:
         return None
     scheme_norm = str(scheme).lower()
     if bucket_packed and (scheme_norm != "qsgd" or bucket_size is None):
         raise ValueError(f"bucket_packed requires scheme='qsgd' and a bucket_size (got scheme={scheme!r}, "
                          f"bucket_size={bucket_size!r})")
+    if (bucket_norm != "l2" or rotate) and scheme_norm != "qsgd":
+        raise ValueError(f"bucket_norm and rotate require scheme='qsgd' (got scheme={scheme!r})")
     if bucket_size is not None and scheme_norm != "qsgd":
         raise ValueError(f"bucket_size requires scheme='qsgd' (got scheme={scheme!r})")
     if value_bits is not None and scheme_norm != "topk":
@@ -126,7 +134,8 @@ def build_global_compressor(*, enabled: bool, scheme: str = "topk", compress_rat
                                value_bits=value_bits)
     if scheme_norm == "qsgd":
         return QSGDQuantCompression(bit_width=int(bit_width), device=device, packed_wire=bool(packed_wire),
-                                    bucket_size=bucket_size, bucket_packed=bool(bucket_packed))
+                                    bucket_size=bucket_size, bucket_packed=bool(bucket_packed),
+                                    bucket_norm=str(bucket_norm), rotate=bool(rotate), rotation_seed=rotation_seed)
     raise ValueError(f"Unsupported global_compression.scheme={scheme!r}; expected 'topk' or 'qsgd'")
 
 
@@ -164,9 +173,13 @@ def hybrid_global_compressor_from_cfg(cfg, device="cpu") -> Optional[GlobalHybri
     value_bits = _select(cfg, "engine.hybrid.global_compression.value_bits", None)  # opt-in, ours
     bucket_size = _select(cfg, "engine.hybrid.global_compression.bucket_size", None)  # opt-in, ours
     bucket_packed = bool(_select(cfg, "engine.hybrid.global_compression.bucket_packed", False))  # opt-in, ours
+    bucket_norm = str(_select(cfg, "engine.hybrid.global_compression.bucket_norm", "l2"))  # opt-in, ours
+    rotate = bool(_select(cfg, "engine.hybrid.global_compression.bucket_rotate", False))  # opt-in, ours
+    rotation_seed = _select(cfg, "engine.hybrid.global_compression.rotation_seed", 0)  # opt-in, ours
     return build_global_compressor(enabled=enabled, scheme=scheme, compress_ratio=ratio, bit_width=bit_width,
                                    device=device, packed_wire=packed, value_bits=value_bits, bucket_size=bucket_size,
-                                   bucket_packed=bucket_packed)
+                                   bucket_packed=bucket_packed, bucket_norm=bucket_norm, rotate=rotate,
+                                   rotation_seed=rotation_seed)
 
 
 # ---------------------------------------------------------------- layer builders (host)
@@ -211,13 +224,17 @@ def qsgd_packed_layer_from_payload(name: str, shape, packed: bytes, norm: float,
 
 
 def qsgd_bucketed_layer_from_payload(name: str, shape, payload: bytes, bnorms, width: int, levels: int,
-                                     bucket_size: int):
+                                     bucket_size: int, rotation_seed: Optional[int] = None):
     """The opt-in bucketed QSGD ``LayerState``: the QSGD layer's values, width and level; ``meta_tensor`` = the
-    tensor's ceil(n / d) fp32 bucket norms (little-endian), and d in ``param_shape``."""
+    tensor's ceil(n / d) fp32 bucket norms (little-endian), and d in ``param_shape``.  ``rotation_seed``: a
+    ``QSGDRotatedBucketedCompression`` layer, ``param_shape = [d, rotation_seed]``."""
     layer = qsgd_layer_from_payload(name, shape, payload, 0.0, width, levels)
     layer.compression_type = QSGD_BUCKETED_COMPRESSION_NAME
     layer.meta_tensor = np.ascontiguousarray(bnorms, dtype="<f4").tobytes()
     layer.param_shape.append(int(bucket_size))
+    if rotation_seed is not None:
+        layer.compression_type = QSGD_ROTATED_BUCKETED_COMPRESSION_NAME
+        layer.param_shape.append(int(rotation_seed))
     return layer
 
 
@@ -520,7 +537,10 @@ def _check_packed_fields(layer):
 def _check_bucketed_fields(layer):
     """The bucketed layer's fields: the bucket size, one norm per bucket, the plain layer's width and level — or,
     on the bit-packed wire, the packed layer's (width = packed_bits(level))."""
-    d = int(layer.param_shape[0]) if len(layer.param_shape) == 1 else 0
+    rotated = layer.compression_type == QSGD_ROTATED_BUCKETED_COMPRESSION_NAME  # param_shape = [d, rotation_seed]
+    d = int(layer.param_shape[0]) if len(layer.param_shape) == (2 if rotated else 1) else 0
+    if rotated and d and layer.param_shape[1] < 0:
+        _field_error(layer, f"QSGD layer {layer.layer_name!r} has invalid rotation seed {layer.param_shape[1]}")
     if d not in codec.BUCKET_SIZES:
         _field_error(layer, f"QSGD layer {layer.layer_name!r} has unsupported bucket size {list(layer.param_shape)}")
     nb = -(-_layer_numel(layer) // d)
@@ -771,7 +791,8 @@ def qsgd_layers_from_arena(plan, q: torch.Tensor, norms: torch.Tensor, names, sh
 
 
 def qsgd_bucketed_layers_from_arena(plan, q: torch.Tensor, bnorms: torch.Tensor, names, shapes, levels: int,
-                                    bucket_size: int, stream=None, packed: bool = False) -> list:
+                                    bucket_size: int, stream=None, packed: bool = False,
+                                    rotation_seed: Optional[int] = None) -> list:
     """``qsgd_layers_from_arena`` for a bucketed encode: the bucket-norm arena copied first, then the payload
     arena in chunks.  A tensor whose bucket norms are all zero gets ``None`` (the dense passthrough).
     ``packed``: ``q`` is the packed arena of ``qsgd_encode_bucketed_packed`` (tensor t's stream at byte
@@ -799,7 +820,8 @@ def qsgd_bucketed_layers_from_arena(plan, q: torch.Tensor, bnorms: torch.Tensor,
         if packed:
             layers[k] = qsgd_bucketed_packed_layer_from_payload(names[k], shapes[k], payload, mine[k], levels, bucket_size)
         else:
-            layers[k] = qsgd_bucketed_layer_from_payload(names[k], shapes[k], payload, mine[k], width, levels, bucket_size)
+            layers[k] = qsgd_bucketed_layer_from_payload(names[k], shapes[k], payload, mine[k], width, levels, bucket_size,
+                                                         rotation_seed)
     return layers
 
 
@@ -823,11 +845,14 @@ def _encode_updates(updates, compressor, weight) -> list:
             groups = []
             for plan, q, bn, members in encode_bucketed(flats, compressor.s, compressor.bucket_size, dev,
                                                         compressor._next_call(), alpha=_alpha(weight),
-                                                        key=compressor.philox_key(), packed=compressor.bucket_packed):
+                                                        key=compressor.philox_key(), packed=compressor.bucket_packed,
+                                                        norm=compressor.bucket_norm,
+                                                        rotation_seed=compressor.wire_rotation_seed):
                 idx = [comp_idx[m] for m in members]
                 got = qsgd_bucketed_layers_from_arena(plan, q, bn, [names[i] for i in idx],
                                                       [tuple(updates[names[i]].shape) for i in idx], levels,
-                                                      compressor.bucket_size, packed=compressor.bucket_packed)
+                                                      compressor.bucket_size, packed=compressor.bucket_packed,
+                                                      rotation_seed=compressor.wire_rotation_seed)
                 for i, L in zip(idx, got):
                     layers[i] = L
         else:
@@ -872,6 +897,9 @@ def _decode_qsgd_batch(layers, dev: torch.device, host: bool = False):
         qd = torch.empty(plan.payload_elems(width), dtype=_QSGD_TORCH_DTYPES[width], device=dev)
         items = [(o * isz, (lambda L=L: L.values_data)) for L, o in zip(layers, plan.offsets)]
         hostio.bytes_to_device(items, qd, isz * plan.arena_end, check=lambda i, p: _check_qsgd_payload(layers[i], p))
+        if layers[0].compression_type == QSGD_ROTATED_BUCKETED_COMPRESSION_NAME:  # and the seed (_scan_layers)
+            return plan.qsgd_decode_bucketed_rot(qd, width, level, d, int(layers[0].param_shape[1]),
+                                                 torch.from_numpy(bn).to(dev), tensor_keyed=False), plan
         return plan.qsgd_decode_bucketed(qd, width, level, d, torch.from_numpy(bn).to(dev)), plan
     norms = np.zeros(plan.nt, dtype=np.float32)
     for i, L in enumerate(layers):
@@ -1071,7 +1099,7 @@ def _validate_layer(layer):
 
 def _scan_layers(proto_layers):
     """Validate every layer in message order.  Returns the QSGD layers grouped by (type, width,
-    level; bucketed layers also by their bucket size) and the Top-K layers with their payloads
+    level; bucketed layers also by their bucket size, rotated ones by their seed too) and the Top-K layers with their payloads
     ``[(layer, values, indices, k)]``."""
     groups: Dict[tuple, list] = {}
     topk: List[tuple] = []
@@ -1080,7 +1108,7 @@ def _scan_layers(proto_layers):
         if got is not None:
             topk.append((L, *got))
         elif L.compression_type in _QSGD_BUCKET_TYPES:
-            groups.setdefault((L.compression_type, L.width, L.level, int(L.param_shape[0])), []).append(L)
+            groups.setdefault((L.compression_type, L.width, L.level, *(int(v) for v in L.param_shape)), []).append(L)
         elif L.compression_type in _QSGD_TYPES:
             groups.setdefault((L.compression_type, L.width, L.level), []).append(L)
     return groups, topk

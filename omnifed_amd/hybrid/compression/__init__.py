@@ -6,7 +6,7 @@ from .core import (
     ResidualUpdates,
     layerwise_decompress,
 )
-from .qsgd import (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME, QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME,
+from .qsgd import (QSGD_ROTATED_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME, QSGD_COMPRESSION_NAME, QSGD_PACKED_COMPRESSION_NAME,
                    QSGDQuantCompression)
 from .topk import (TOPK_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME,
                    TopKCompression)
@@ -23,6 +23,7 @@ __all__ = [
     "QSGD_COMPRESSION_NAME",
     "QSGD_PACKED_COMPRESSION_NAME",
     "QSGD_BUCKETED_COMPRESSION_NAME",
+    "QSGD_ROTATED_BUCKETED_COMPRESSION_NAME",
     "QSGD_BUCKETED_PACKED_COMPRESSION_NAME",
     "layerwise_decompress",
 ]

@@ -31,6 +31,7 @@ upcast: ``omf_qsgd_encode_h16``); float64 tensors raise ``ValueError`` (no fp64 
 
 from __future__ import annotations
 
+import functools
 import itertools
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -51,6 +52,10 @@ QSGD_BUCKETED_COMPRESSION_NAME = "QSGDBucketedCompression"
 # param_shape = [d], the packed layer's codes, width = packed_bits(level) and values_dtype "packed.u{b}"
 # (include/omf_codec.h omf_qsgd_encode_bucketed_packed: the codes leave the encode pass already packed).
 QSGD_BUCKETED_PACKED_COMPRESSION_NAME = "QSGDBucketedPackedCompression"
+# Opt-in max-scaled buckets with the randomised Hadamard rotation (not reference-compatible): the bucketed layer
+# with the scales max |z| in meta_tensor and param_shape = [d, rotation_seed]; the signs are keyed by the seed and
+# the element alone (tensor_keyed = 0, include/omf_codec.h), so a receiver needs nothing else to invert the layer.
+QSGD_ROTATED_BUCKETED_COMPRESSION_NAME = "QSGDRotatedBucketedCompression"
 
 
 def should_compress_tensor(x: torch.Tensor) -> bool:
@@ -101,7 +106,8 @@ def _arena(flats: Sequence[torch.Tensor], dev: torch.device, plan) -> torch.Tens
 
 
 def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: int, dev: torch.device,
-                    call_index: int = 0, alpha: float = 1.0, key: int = 0, packed: bool = False):
+                    call_index: int = 0, alpha: float = 1.0, key: int = 0, packed: bool = False, norm: str = "l2",
+                    rotation_seed: Optional[int] = None):
     """Encode flat fp32 / bf16 / fp16 tensors with bucket norms, ONE launch per dtype present (normally one;
     ``Plan.qsgd_encode_bucketed``, on-device draws).  Returns ``[(plan, q_arena, bnorms_dev, members)]`` in
     order of first appearance, as ``encode_groups``: ``members[k]`` is the index into ``flats`` of the plan's
@@ -109,7 +115,13 @@ def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: 
     stream offset = ``call_index``.  ``packed``: ``Plan.qsgd_encode_bucketed_packed``, ``q_arena`` the packed
     arena (``qsgd_pack``'s layout).  bf16 / fp16 tensors are read from a 16-bit arena — the buffer they already
     share at the plan's offsets (``shared_arena``), else one they are gathered into bit for bit — and encoded
-    as their exact fp32 upcast would be (omf_qsgd_encode_bucketed_h16): no fp32 copy at any size."""
+    as their exact fp32 upcast would be (omf_qsgd_encode_bucketed_h16): no fp32 copy at any size.
+    ``norm="max"``: every bucket scaled by its max |v| (``Plan.qsgd_encode_bucketed_max``; fp32 tensors, the int8 /
+    int32 wire); the arenas returned read as the L2 ones do.  ``rotation_seed`` (an int, with ``norm="max"``): full
+    buckets are rotated first, the signs keyed by the seed and the element alone (``tensor_keyed=False``)."""
+    if norm == "max" and (packed or any(f.dtype != torch.float32 for f in flats)):
+        raise ValueError("bucket_norm='max' encodes float32 tensors on the int8 / int32 wire (no bucket_packed, no "
+                         "bfloat16 / float16 tensor)")
     members: Dict[torch.dtype, List[int]] = {}
     for i, f in enumerate(flats):
         value_format(f.dtype)
@@ -119,6 +131,9 @@ def encode_bucketed(flats: Sequence[torch.Tensor], bit_width: int, bucket_size: 
         plan = codec.Plan.get([int(flats[i].numel()) for i in idx], device=dev)
         x = gather_arena([flats[i] for i in idx], dev, plan, dt)
         encode = plan.qsgd_encode_bucketed_packed if packed else plan.qsgd_encode_bucketed
+        if norm == "max":
+            encode = functools.partial(plan.qsgd_encode_bucketed_max, rotate=rotation_seed is not None,
+                                       rotation_seed=rotation_seed or 0, tensor_keyed=False)
         q, bn = encode(x, int(bit_width), bucket_size, alpha=alpha, seed=(int(key) + g) & (2**64 - 1), offset=call_index)
         out.append((plan, q, bn, idx))
     return out
@@ -226,7 +241,8 @@ class QSGDQuantCompression(Compression):
     """QSGD (Alistarh et al., 2017), Algorithm 1 — on the GPU."""
 
     def __init__(self, bit_width: int = 8, device="cpu", rng: str = "philox", packed_wire: bool = False,
-                 bucket_size: Optional[int] = None, bucket_packed: bool = False):
+                 bucket_size: Optional[int] = None, bucket_packed: bool = False, bucket_norm: str = "l2",
+                 rotate: bool = False, rotation_seed: int = 0):
         super().__init__()
         self.s = int(bit_width)
         self.packed_wire = bool(packed_wire)  # encode_updates_dict / encode_layer_state emit packed layers
@@ -248,10 +264,31 @@ class QSGDQuantCompression(Compression):
         self.bucket_packed = bool(bucket_packed)
         if self.bucket_packed and self.bucket_size is None:
             raise ValueError("bucket_packed=True requires bucket_size")
+        # opt-in: a bucket's scale is its max |v| instead of its L2 norm (omf_qsgd_encode_bucketed_max); the layers
+        # are ordinary QSGDBucketedCompression ones, read by every bucketed decoder and the PS unchanged
+        if bucket_norm not in ("l2", "max"):
+            raise ValueError(f"unknown bucket_norm={bucket_norm!r}; expected 'l2' or 'max'")
+        if bucket_norm == "max" and self.bucket_size is None:
+            raise ValueError("bucket_norm='max' requires bucket_size")
+        if bucket_norm == "max" and self.bucket_packed:
+            raise ValueError("bucket_norm='max' and bucket_packed=True cannot be combined")
+        self.bucket_norm = bucket_norm
+        # opt-in: full buckets are rotated by a randomised Hadamard transform before quantising
+        # (QSGDRotatedBucketedCompression layers); only with the max scale (with the L2 scale it loses accuracy)
+        if rotate and bucket_norm != "max":
+            raise ValueError("rotate=True requires bucket_norm='max'")
+        if isinstance(rotation_seed, bool) or not isinstance(rotation_seed, int) or not 0 <= rotation_seed < 2**31:
+            raise ValueError(f"rotation_seed={rotation_seed!r}: expected an int in [0, 2^31)")
+        self.rotate, self.rotation_seed = bool(rotate), rotation_seed
         self.rng = rng
         self._calls = 0
         self._instance = next(_INSTANCES)
         self.client_id: Optional[int] = None  # None: client_identity() (the process's rank)
+
+    @property
+    def wire_rotation_seed(self) -> Optional[int]:
+        """The rotation seed of this compressor's layers, or None where it does not rotate."""
+        return self.rotation_seed if self.rotate else None
 
     def philox_key(self) -> int:
         """The Philox key of this compressor (see the module docstring)."""
@@ -290,7 +327,8 @@ class QSGDQuantCompression(Compression):
         if self.bucket_size is not None:  # norm: the tensor's bucket norms, a 1-D fp32 CPU tensor
             res: List[Tuple] = [None] * len(flats)
             for plan, q, bn, idx in encode_bucketed(flats, self.s, self.bucket_size, dev, self._next_call(),
-                                                    alpha=alpha, key=self.philox_key()):
+                                                    alpha=alpha, key=self.philox_key(), norm=self.bucket_norm,
+                                                    rotation_seed=self.wire_rotation_seed):
                 host = bn.cpu()  # synchronises the stream
                 boff, nb = plan.bucket_layout(self.bucket_size)
                 for i, o, n, b0, b1 in zip(idx, plan.offsets, plan.sizes, boff, boff[1:] + [nb]):
@@ -321,9 +359,9 @@ class QSGDQuantCompression(Compression):
 
     @staticmethod
     def decompress_quantized(signed_levels: torch.Tensor, norm, levels: int, shape,
-                             bucket_size: Optional[int] = None) -> torch.Tensor:
+                             bucket_size: Optional[int] = None, rotation_seed: Optional[int] = None) -> torch.Tensor:
         """qsgd.py:84-96: ``norm * signed_level / levels`` (fp32), on the GPU.  ``bucket_size`` (ours): ``norm``
-        is the tensor's 1-D fp32 bucket norms, as a bucketed ``compress`` returns them."""
+        is the tensor's 1-D fp32 bucket norms, as a bucketed ``compress`` returns them; ``rotation_seed``: of a rotating one."""
         if levels <= 0 or norm is None or (not isinstance(norm, torch.Tensor) and norm == -1):
             return signed_levels
         out_dev = signed_levels.device
@@ -348,7 +386,11 @@ class QSGDQuantCompression(Compression):
             bn = torch.as_tensor(norm, dtype=torch.float32).reshape(-1)
             if bn.numel() != nb:
                 raise ValueError(f"{bn.numel()} bucket norms for {n} elements in buckets of {bucket_size}: expected {nb}")
-            y = plan.qsgd_decode_bucketed(qbuf, width, int(levels), bucket_size, bn.to(dev).contiguous())
+            if rotation_seed is not None:
+                y = plan.qsgd_decode_bucketed_rot(qbuf, width, int(levels), bucket_size, rotation_seed,
+                                                  bn.to(dev).contiguous(), tensor_keyed=False)
+            else:
+                y = plan.qsgd_decode_bucketed(qbuf, width, int(levels), bucket_size, bn.to(dev).contiguous())
             return y[:n].reshape(shape).to(out_dev)
         nrm = torch.tensor([float(norm)], dtype=torch.float32, device=dev)
         y = plan.qsgd_decode(qbuf, width, int(levels), nrm)
@@ -359,4 +401,5 @@ class QSGDQuantCompression(Compression):
         with ``bucket_size``)."""
         norm, _width, levels, shape = ctx
         signed_levels = tensors[0] if isinstance(tensors, (tuple, list)) else tensors
-        return self.decompress_quantized(signed_levels, norm, levels, shape, bucket_size=self.bucket_size)
+        return self.decompress_quantized(signed_levels, norm, levels, shape, bucket_size=self.bucket_size,
+                                         rotation_seed=self.wire_rotation_seed)

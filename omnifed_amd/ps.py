@@ -177,12 +177,13 @@ class DeviceAggregator:
         code's bits; an update's QSGD layers are all packed or all plain.  ``QSGDBucketedCompression`` layers
         (one bucket size per update, never mixed with the other two) give ``packed = ("bucket", d)`` and
         ``norms`` the plan's bucket-norm arena; ``QSGDBucketedPackedCompression`` layers (likewise)
-        ``packed = ("bucket_packed", d)``, ``payload`` the packed arena and ``width`` the code's bits."""
+        ``packed = ("bucket_packed", d)``, ``payload`` the packed arena and ``width`` the code's bits;
+        ``QSGDRotatedBucketedCompression`` layers ``packed = ("bucket_rot", d, rotation seed)`` (one of each per update)."""
         from .hybrid.communicator.global_grpc_compression import (_check_qsgd_payload, _decode_topk_layer,
                                                                   _validate_layer, check_topk_indices, stage_topk)
         from .hybrid.communicator.global_grpc_compression import QuantValues
         from .hybrid.compression import (QSGD_BUCKETED_COMPRESSION_NAME, QSGD_BUCKETED_PACKED_COMPRESSION_NAME,
-                                         QSGD_PACKED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME,
+                                         QSGD_PACKED_COMPRESSION_NAME, QSGD_ROTATED_BUCKETED_COMPRESSION_NAME, TOPK_PACKED_COMPRESSION_NAME,
                                          TOPK_QUANT_COMPRESSION_NAME)
 
         last: Dict[str, object] = {}
@@ -197,7 +198,7 @@ class DeviceAggregator:
         kept = sorted(last.values(), key=lambda L: self.index[L.layer_name])  # ascending arena offsets
         packed_topk = (TOPK_PACKED_COMPRESSION_NAME, TOPK_QUANT_COMPRESSION_NAME)
         qsgd_types = ("QSGDQuantCompression", QSGD_PACKED_COMPRESSION_NAME, QSGD_BUCKETED_COMPRESSION_NAME,
-                      QSGD_BUCKETED_PACKED_COMPRESSION_NAME)
+                      QSGD_BUCKETED_PACKED_COMPRESSION_NAME, QSGD_ROTATED_BUCKETED_COMPRESSION_NAME)
         topk_types = ("TopKCompression", *packed_topk)
         known = (*qsgd_types, *topk_types, "")
         qsgd = [L for L in kept if L.compression_type in qsgd_types]
@@ -215,8 +216,10 @@ class DeviceAggregator:
                 packed = ("bucket", int(qsgd[0].param_shape[0]))
             if qsgd[0].compression_type == QSGD_BUCKETED_PACKED_COMPRESSION_NAME:
                 packed = ("bucket_packed", int(qsgd[0].param_shape[0]))
+            if qsgd[0].compression_type == QSGD_ROTATED_BUCKETED_COMPRESSION_NAME:  # ("bucket_rot", d, rotation seed)
+                packed = ("bucket_rot", int(qsgd[0].param_shape[0]), int(qsgd[0].param_shape[1]))
             if any(L.compression_type != qsgd[0].compression_type
-                   or (isinstance(packed, tuple) and int(L.param_shape[0]) != packed[1]) for L in qsgd):
+                   or (isinstance(packed, tuple) and tuple(int(v) for v in L.param_shape) != packed[1:]) for L in qsgd):
                 raise ValueError("mixed QSGD width/level within one update (one wire per update: plain, bit-packed, "
                                  "bucketed or packed bucketed of one bucket size)")
             if any(L.width != width or L.level != level for L in qsgd):
@@ -320,6 +323,9 @@ class DeviceAggregator:
                 self.plan.qsgd_decode_packed(qd, level, nd, y_out=self.acc, accumulate=True)
             elif packed and packed[0] == "bucket_packed":
                 self.plan.qsgd_decode_bucketed_packed(qd, level, packed[1], nd, y_out=self.acc, accumulate=True)
+            elif packed and packed[0] == "bucket_rot":
+                self.plan.qsgd_decode_bucketed_rot(qd, width, level, packed[1], packed[2], nd, y_out=self.acc,
+                                                   accumulate=True, tensor_keyed=False)
             elif packed:  # ("bucket", d)
                 self.plan.qsgd_decode_bucketed(qd, width, level, packed[1], nd, y_out=self.acc, accumulate=True)
             else:
@@ -367,6 +373,10 @@ class DeviceAggregator:
             elif packed and packed[0] == "bucket_packed":  # a run shares (level, d)
                 self.plan.qsgd_decode_sum_bucketed_packed([b[0][0] for b in batch], level, packed[1],
                                                           [b[0][3] for b in batch], y_out=self.acc, init=True)
+            elif packed and packed[0] == "bucket_rot":  # a run shares (width, level, d, rotation seed): one inverse
+                self.plan.qsgd_decode_sum_bucketed_rot([b[0][0] for b in batch], width, level, packed[1], packed[2],
+                                                       [b[0][3] for b in batch], y_out=self.acc, init=True,
+                                                       tensor_keyed=False)
             elif packed:  # ("bucket", d): a run shares (width, level, d)
                 self.plan.qsgd_decode_sum_bucketed([b[0][0] for b in batch], width, level, packed[1],
                                                    [b[0][3] for b in batch], y_out=self.acc, init=True)
@@ -561,6 +571,7 @@ class DeviceAggregator:
         from .hybrid.compression.qsgd import QSGDQuantCompression
         return (self.fuse_bucketed_step and isinstance(compressor, QSGDQuantCompression)
                 and compressor.bucket_size is not None and compressor.rng == "philox" and self.compute_mean
+                and compressor.bucket_norm == "l2"  # the fused step's downlink encode scales by the L2 norm
                 and 0 <= compressor.s <= 30 and float(total) != 0.0 and bool(self.names)
                 and all(numel(self.shapes[n]) > 0 for n in self.names))
 
@@ -611,7 +622,8 @@ class DeviceAggregator:
             raise
 
         def bucketed_only(st):
-            return st[0] is not None and st[1] is None and not st[2] and isinstance(st[0][4], tuple)
+            return (st[0] is not None and st[1] is None and not st[2] and isinstance(st[0][4], tuple)
+                    and st[0][4][0] != "bucket_rot")  # the fused step sums in the unrotated domain
 
         tail = len(staged)
         while (tail > 0 and len(staged) - tail < max(int(max_batch), 1) and bucketed_only(staged[tail - 1][0])
