@@ -65,7 +65,7 @@ extern "C" {
 typedef struct omf_plan omf_plan;
 
 /* ABI version (major*100 + minor). */
-#define OMF_ABI_VERSION 122
+#define OMF_ABI_VERSION 123
 int omf_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -136,7 +136,8 @@ int32_t omf_plan_encode_strategy(const omf_plan* plan);
  * bucketed encoder that packs its codes (omf_qsgd_encode_bucketed_packed), 9 the bucketed PS step's fused launch
  * (omf_ps_sum_encode_bucketed), 10 / 11 the bucketed encoders of a 16-bit arena (omf_qsgd_encode_bucketed_h16 /
  * omf_qsgd_encode_bucketed_packed_h16), 12 / 13 the max-scaled bucketed encoder without / with its rotation
- * (omf_qsgd_encode_bucketed_max); -1 before the first.  Lets a test assert which path a configuration takes (e.g. the int32
+ * (omf_qsgd_encode_bucketed_max), 14 the max-scaled PS step's fused launch (omf_ps_sum_encode_bucketed_max); -1 before
+ * the first.  Lets a test assert which path a configuration takes (e.g. the int32
  * wire of a bracketed plan: the ring). */
 int32_t omf_plan_last_encoder(const omf_plan* plan);
 
@@ -514,6 +515,38 @@ int omf_ps_sum_encode_bucketed(omf_plan* plan, const float* acc, const void* con
                                int32_t nclients, int32_t width_in, int32_t levels_in, int64_t bucket_in, float* sum_out,
                                float divisor, float* avg_out, int32_t bit_width, int64_t bucket_out, int32_t pack_out,
                                uint64_t seed, uint64_t offset, void* q_out, float* bnorm_out, void* stream);
+
+/*
+ * omf_ps_sum_encode_bucketed for max-scaled payloads, rotated or not (omf_qsgd_encode_bucketed_max's wire, int8 /
+ * int32 levels): nclients payloads of one (width_in, levels_in, bucket_size, rotate, rot_seed, tensor_keyed) summed
+ * in array order, the sum taken back from the rotated domain and added to acc, divided, and the average re-encoded
+ * by the same quantiser with the same bucket size and rotation — in ONE launch that reads every payload (and acc)
+ * once and writes the average once.  acc, q_in / bnorm_in, sum_out, avg_out, divisor as omf_ps_sum_encode_bucketed.
+ * requantise_rotated == 0: on the tensors' elements avg_out (and sum_out) hold the bytes of this sequence:
+ * omf_qsgd_decode_sum_bucketed (rotate == 0) or omf_qsgd_decode_sum_bucketed_rot (rotate != 0) with
+ * init = (acc != NULL) and divisor 0 into a copy of acc — with that call's grouping of more than 8 clients: without
+ * acc one client-order sum in the rotated domain and one inverse, with acc each group of 8 inverted and added in
+ * turn — the store of that sum to sum_out, omf_div_f32 by divisor (0: no division) into avg_out; q_out / bnorm_out
+ * hold the bytes of omf_qsgd_encode_bucketed_max(avg_out, alpha = 1, bit_width, bucket_size, NULL, seed, offset,
+ * NULL, q_out, bnorm_out, rotate, rot_seed, tensor_keyed).  Every valid call is served by the fused kernel, any
+ * levels_in included; one launch takes 8 clients on the int8 wire and 4 on the int32 wire, the leading groups of
+ * a longer call leave their sum in sum_out (without it in avg_out, which the last launch reads in place); a
+ * rotated call onto acc of more clients than one launch takes runs omf_qsgd_decode_sum_bucketed_rot for every
+ * group but a last one that fits.
+ * requantise_rotated != 0 (needs rotate != 0 and acc == NULL): avg_out and sum_out as above; q_out / bnorm_out
+ * hold the bytes of omf_qsgd_encode_bucketed_max(W, alpha = 1, ..., rotate = 0) with W = Z / divisor, Z the
+ * clients' sum in the rotated domain (on a tensor's short last bucket, which is never rotated, the sum itself).
+ * H_d H_d = d I, so W is the forward transform of the average up to rounding: a receiver decodes q_out as any
+ * rotated payload, and no forward transform runs.  The downlink's bytes differ from the exact form's.
+ * omf_plan_last_encoder returns 14.  Padding is not written.  Philox draws only.  No in-kernel wait.
+ * OMF_EINVAL, with nothing launched: as omf_ps_sum_encode_bucketed (width_in 8 or 32 only), and
+ * requantise_rotated with rotate == 0 or with acc.
+ */
+int omf_ps_sum_encode_bucketed_max(omf_plan* plan, const float* acc, const void* const* q_in, const float* const* bnorm_in,
+                                   int32_t nclients, int32_t width_in, int32_t levels_in, int64_t bucket_size,
+                                   int32_t rotate, uint32_t rot_seed, int32_t tensor_keyed, int32_t requantise_rotated,
+                                   float* sum_out, float divisor, float* avg_out, int32_t bit_width, uint64_t seed,
+                                   uint64_t offset, void* q_out, float* bnorm_out, void* stream);
 
 /*
  * Top-K sparsification with error feedback, all tensors of the plan in one call.

@@ -103,6 +103,9 @@ SIGNATURES = {
     "omf_ps_sum_encode_bucketed": (ctypes.c_int, [_c_p, _c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32, _c_i32,
                                                   _c_i32, _c_i64, _c_p, _c_f32, _c_p, _c_i32, _c_i64, _c_i32, _c_u64,
                                                   _c_u64, _c_p, _c_p, _c_p]),
+    "omf_ps_sum_encode_bucketed_max": (ctypes.c_int, [_c_p, _c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), _c_i32,
+                                                      _c_i32, _c_i32, _c_i64, _c_i32, ctypes.c_uint32, _c_i32, _c_i32,
+                                                      _c_p, _c_f32, _c_p, _c_i32, _c_u64, _c_u64, _c_p, _c_p, _c_p]),
     "omf_qsgd_packed_bits": (_c_i32, [_c_i32]),
     "omf_qsgd_pack": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "omf_qsgd_decode_packed": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p]),
@@ -144,7 +147,7 @@ class CodecError(RuntimeError):
     pass
 
 
-ABI_VERSION = 122 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
+ABI_VERSION = 123 # include/omf_codec.h OMF_ABI_VERSION; a library of another version is refused
 
 
 def lib() -> ctypes.CDLL:

@@ -19,7 +19,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libomf_codec.so")
 
 SOURCES = ["omf_runtime.cpp", "omf_plan_layout.cpp", "omf_qsgd.hip", "omf_qsgd_recv.hip", "omf_qsgd_bracket.hip",
-           "omf_qsgd_ring.hip", "omf_qsgd_h16.hip", "omf_qsgd_bucketed.hip", "omf_qsgd_bucket_pack.hip", "omf_qsgd_bucket_ps.hip", "omf_qsgd_bucket_h16.hip", "omf_qsgd_bucket_rot.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_sampled.hip", "omf_topk_exact.hip",
+           "omf_qsgd_ring.hip", "omf_qsgd_h16.hip", "omf_qsgd_bucketed.hip", "omf_qsgd_bucket_pack.hip", "omf_qsgd_bucket_ps.hip", "omf_qsgd_bucket_h16.hip", "omf_qsgd_bucket_rot.hip", "omf_qsgd_bucket_ps_max.hip", "omf_qsgd_pack.hip", "omf_topk.hip", "omf_topk_sampled.hip", "omf_topk_exact.hip",
            "omf_topk_recv.hip", "omf_topk_tie.hip", "omf_topk_pack.hip", "omf_topk_qval.hip", "omf_topk_host.cpp", "omf_topk_layout.cpp"]
 
 # Exact IEEE fp32 (no contraction, denormals kept, correctly rounded / and sqrt): the
@@ -41,7 +41,7 @@ FLAGS = [
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"omf_qsgd_h16.hip": _NO_PK_F32, "omf_qsgd_bucketed.hip": _NO_PK_F32, "omf_qsgd_bucket_pack.hip": _NO_PK_F32,
               "omf_qsgd_bucket_ps.hip": _NO_PK_F32, "omf_qsgd_bucket_h16.hip": _NO_PK_F32,
-              "omf_qsgd_bucket_rot.hip": _NO_PK_F32}
+              "omf_qsgd_bucket_rot.hip": _NO_PK_F32, "omf_qsgd_bucket_ps_max.hip": _NO_PK_F32}
 
 
 def hipcc() -> str:

@@ -312,11 +312,13 @@ class Plan:
         "norm_in" (levels with caller norms), "h16" (a bf16 / fp16 arena), "bucketed" (bucket norms),
         "bucketed_packed" (bucket norms, codes packed in the pass), "bucketed_ps" (the bucketed PS step's fused
         launch), "bucketed_h16" / "bucketed_packed_h16" (the bucketed encoders of a bf16 / fp16 arena), "bucketed_max" /
-        "bucketed_max_rot" (max-scaled buckets without / with the Hadamard rotation) or "none"."""
+        "bucketed_max_rot" (max-scaled buckets without / with the Hadamard rotation), "bucketed_ps_max" (the max-scaled
+        PS step's fused launch) or "none"."""
         code = int(lib().omf_plan_last_encoder(self._h))
         return STRATEGIES[code] if 0 <= code < len(STRATEGIES) else {
             5: "norm_in", 6: "h16", 7: "bucketed", 8: "bucketed_packed", 9: "bucketed_ps",
-            10: "bucketed_h16", 11: "bucketed_packed_h16", 12: "bucketed_max", 13: "bucketed_max_rot"}.get(code, "none")
+            10: "bucketed_h16", 11: "bucketed_packed_h16", 12: "bucketed_max", 13: "bucketed_max_rot",
+            14: "bucketed_ps_max"}.get(code, "none")
 
     @property
     def encoder_kernel(self) -> str:
@@ -1028,6 +1030,66 @@ class Plan:
                 self._h, _ptr(acc), qp, npp, n, wi, li, int(bucket_in), _ptr(sum_out), d, _ptr(avg_out), s,
                 int(bucket_out), 1 if pack_out else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
                 _ptr(q_out), _ptr(bnorm_out), ctypes.c_void_p(st)), "omf_ps_sum_encode_bucketed")
+        return avg_out, q_out, bnorm_out
+
+    def ps_sum_encode_bucketed_max(self, acc: Optional[torch.Tensor], q_in: Sequence[torch.Tensor],
+                                   bnorm_in: Sequence[torch.Tensor], width_in: int, levels_in: int, bucket_size: int,
+                                   divisor: Optional[float], bit_width: int, rotate: bool = False,
+                                   rotation_seed: int = 0, tensor_keyed: bool = True, requantise_rotated: bool = False,
+                                   sum_out: Optional[torch.Tensor] = None, avg_out: Optional[torch.Tensor] = None,
+                                   seed: int = 0, offset: int = 0, q_out: Optional[torch.Tensor] = None,
+                                   bnorm_out: Optional[torch.Tensor] = None, stream: Optional[int] = None):
+        """``ps_sum_encode_bucketed`` for max-scaled payloads, rotated or not (omf_ps_sum_encode_bucketed_max): the
+        bytes of ``qsgd_decode_sum_bucketed`` (``rotate``: ``qsgd_decode_sum_bucketed_rot``), ``div_`` and
+        ``qsgd_encode_bucketed_max`` with the same ``bucket_size`` and rotation, in one launch.
+        ``requantise_rotated`` (needs ``rotate`` and no ``acc``): the downlink is quantised from the clients' sum
+        in the rotated domain over the divisor, with no forward transform — other downlink bytes, the same
+        ``avg`` and ``sum``.  Returns ``(avg, q, scales)``."""
+        s, wi, li = int(bit_width), int(width_in), int(levels_in)
+        if not 0 <= s <= 30:
+            raise ValueError("bit_width must be in [0, 30]")
+        if wi not in (8, 32):
+            raise ValueError(f"unsupported width_in={wi}")
+        q_in, bnorm_in = list(q_in), list(bnorm_in)
+        if len(q_in) != len(bnorm_in):
+            raise ValueError(f"ps_sum_encode_bucketed_max needs one scale arena per payload ({len(q_in)}, {len(bnorm_in)})")
+        if not q_in and acc is None:
+            raise ValueError("ps_sum_encode_bucketed_max needs a payload or an accumulator")
+        if q_in and li <= 0:
+            raise ValueError(f"invalid level={li}")
+        if requantise_rotated and (not rotate or acc is not None):
+            raise ValueError("requantise_rotated needs rotate=True and no accumulator")
+        d = 0.0 if divisor is None else float(divisor)
+        if divisor is not None and d == 0.0:
+            raise ValueError("divisor must not be 0 (None: no division)")
+        dev = self.device
+        _, nb = self.bucket_layout(bucket_size)
+        qdt, qal = (torch.int8, 4) if wi == 8 else (torch.int32, 16)
+        for k, (q, nm) in enumerate(zip(q_in, bnorm_in)):
+            _need(q, f"q_in[{k}]", qdt, dev, self.payload_elems(wi), qal)
+            _need(nm, f"bnorm_in[{k}]", torch.float32, dev, nb, 4)
+        for t, name in ((acc, "acc"), (sum_out, "sum_out")):
+            if t is not None:
+                _need(t, name, torch.float32, dev, self.arena_end, 16)
+        if avg_out is None:
+            avg_out = torch.empty(self.arena_end, dtype=torch.float32, device=dev)
+        _need(avg_out, "avg_out", torch.float32, dev, self.arena_end, 16)
+        width = storage_width(2 ** s)
+        odt = torch.int8 if width == 8 else torch.int32
+        if q_out is None:
+            q_out = torch.empty(self.payload_elems(width), dtype=odt, device=dev)
+        _need(q_out, "q_out", odt, dev, self.payload_elems(width), 4 if width == 8 else 16)
+        bnorm_out = self._bucket_norms(bnorm_out, "bnorm_out", nb)
+        n = len(q_in)
+        qp = (ctypes.c_void_p * max(n, 1))(*[q.data_ptr() for q in q_in])
+        npp = (ctypes.c_void_p * max(n, 1))(*[nm.data_ptr() for nm in bnorm_in])
+        st = stream if stream is not None else _stream(dev)
+        with self._lock:  # the first call at a bucket size makes the plan's table
+            check(lib().omf_ps_sum_encode_bucketed_max(
+                self._h, _ptr(acc), qp, npp, n, wi, li, int(bucket_size), 1 if rotate else 0,
+                _rotation_seed(rotation_seed), 1 if tensor_keyed else 0, 1 if requantise_rotated else 0, _ptr(sum_out),
+                d, _ptr(avg_out), s, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(q_out),
+                _ptr(bnorm_out), ctypes.c_void_p(st)), "omf_ps_sum_encode_bucketed_max")
         return avg_out, q_out, bnorm_out
 
     # ------------------------------------------------------------ bit-packed wire (opt-in)

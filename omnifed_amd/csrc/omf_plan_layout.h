@@ -197,6 +197,7 @@ enum Encoder : int32_t {
   kEncBucketedPackedH16 = 11,  // the same on the bit-packed wire (omf_qsgd_bucket_h16.hip): the entry point's
   kEncBucketedMax = 12,        // max-scaled buckets (omf_qsgd_bucket_rot.hip): the entry point's
   kEncBucketedMaxRot = 13,     // the same with the Hadamard rotation (omf_qsgd_bucket_rot.hip): the entry point's
+  kEncBucketedPsMax = 14,      // the max-scaled PS step's fused launch (omf_qsgd_bucket_ps_max.hip): the entry point's
 };
 
 struct Call {

@@ -44,90 +44,6 @@ using namespace omf::plan_layout;
 
 namespace {
 
-using bucket_rot::kBlk;
-using bucket_rot::kRows;
-
-// What every kernel here takes from the plan and the call.
-struct RotGeom {
-  const Item* items;      // the plan's flat items
-  const int64_t* begins;  // per tensor
-  const int64_t* sizes;
-  const int64_t* boff;    // the tensors' offsets into the bucket arena at this d
-  int64_t arena_end;
-  int32_t nt;
-  uint32_t rot_seed;
-  int32_t tensor_mask;    // -1: sigma keyed by the plan's tensor index; 0: by the element alone (every tensor as tensor 0)
-  int32_t logd;
-};
-
-// This workgroup's block [b, end) of tensor `tensor` ([tbegin, tbegin + tn)); b >= end: none.
-struct Blk {
-  int64_t b, end, tbegin, tn;
-  int32_t tensor;
-};
-__device__ __forceinline__ Blk block_of(const RotGeom& g) {
-  constexpr int PER = (int)(kSub / kBlk);
-  const Item it = g.items[blockIdx.x / PER];
-  Blk k;
-  k.b = it.begin + (int64_t)(blockIdx.x % PER) * kBlk;
-  k.end = min(k.b + (int64_t)kBlk, it.end);
-  k.tensor = it.tensor;
-  k.tbegin = g.begins[it.tensor];
-  k.tn = g.sizes[it.tensor];
-  return k;
-}
-
-// The transform of a block's rows in place, forward (z = H (sigma . v)) or inverse (xh = sigma . (H zh) 2^-logd),
-// on the quads of full buckets; the others keep their values.  A FULL block holds full buckets only (d divides
-// 4096).  Called by the whole workgroup, lanes past `end` holding +0: in a mixed block every lane runs the
-// exchanges.
-template <bool INVERSE, bool FULL>
-__device__ __forceinline__ void rotate_block(float (&z)[kRows][4], const RotGeom& g, const Blk& bk, int logd,
-                                             float4* tile) {
-  const int64_t rel = (bk.b - bk.tbegin) + 4 * (int)threadIdx.x;  // this thread's row 0, from the tensor's begin
-  float keep[kRows][4];
-  if (!FULL) {
-#pragma unroll
-    for (int k = 0; k < kRows; ++k)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) keep[k][c] = z[k][c];
-  }
-  if (!INVERSE) {
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) bucket_rot::apply_signs(z[k], g.rot_seed, bk.tensor & g.tensor_mask, rel + 1024 * k);
-  }
-  bucket_rot::wht_rows(z, logd, tile);
-  if (INVERSE) {
-    const float inv_d = __uint_as_float((uint32_t)(127 - logd) << 23);  // 2^-logd
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) z[k][c] = __fmul_rn(z[k][c], inv_d);
-      bucket_rot::apply_signs(z[k], g.rot_seed, bk.tensor & g.tensor_mask, rel + 1024 * k);
-    }
-  }
-  if (!FULL) {
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-      const bool full = ((((rel + 1024 * k) >> logd) + 1) << logd) <= bk.tn;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) z[k][c] = full ? z[k][c] : keep[k][c];
-    }
-  }
-}
-
-// A live quad's (e < end) floats out: one non-temporal 16-byte store when whole, else its elements one by one.
-template <bool FULL>
-__device__ __forceinline__ void store_f4(float* y, int64_t e, int64_t end, const float (&f)[4]) {
-  if (FULL || e + 4 <= end) {
-    store_nt(y + e, make_float4(f[0], f[1], f[2], f[3]));
-  } else {
-    y[e] = f[0];
-    if (e + 1 < end) y[e + 1] = f[1];
-    if (e + 2 < end) y[e + 2] = f[2];
-  }
-}
-
 // ---------------------------------------------------------------- encoder
 
 template <int WIDTH, bool HAS_U, bool ROT, bool FULL>
@@ -235,23 +151,6 @@ __global__ __launch_bounds__(kThreads) void qsgd_bucket_rotate(const float* __re
 
 // ---------------------------------------------------------------- decode and sum
 
-// The levels of the quad at e of a payload whose tensor ends at `end`: raw[0] (WIDTH 1: the dword of four int8)
-// or raw[0..3]; a partial last quad element by element (the payload may end with it), zeros past the end.
-template <int WIDTH, bool FULL>
-__device__ __forceinline__ void load_levels(const void* q, int64_t e, int64_t end, int32_t (&rr)[4]) {
-  rr[0] = rr[1] = rr[2] = rr[3] = 0;
-  if (FULL || e + 4 <= end) {
-    if (WIDTH == 1) {
-      rr[0] = __builtin_nontemporal_load(reinterpret_cast<const int32_t*>(reinterpret_cast<const int8_t*>(q) + e));
-    } else {
-      const i32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(reinterpret_cast<const int32_t*>(q) + e));
-      rr[0] = t[0]; rr[1] = t[1]; rr[2] = t[2]; rr[3] = t[3];
-    }
-  } else if (e < end) {
-    qsgd_last_quad<WIDTH>(q, e, end, rr);
-  }
-}
-
 struct RotSum {
   int32_t from_rot;  // the sum starts from y, a running sum in the rotated domain
   int32_t to_rot;    // the sum is stored as it is: no inverse, no y, no divisor
@@ -329,22 +228,6 @@ __global__ __launch_bounds__(kThreads) void qsgd_bucket_decode_sum_rot(BSumArgs<
 
 // ---------------------------------------------------------------- host side
 
-int geom(omf_plan* p, int logd, uint32_t rot_seed, int32_t tensor_keyed, RotGeom* g) {
-  int64_t nb = 0;
-  if (int r = bucket_tables(p, logd, &g->boff, &nb)) return r;
-  g->items = p->d_flat;
-  g->begins = p->d_begins;
-  g->sizes = p->d_sizes;
-  g->arena_end = p->arena_end;
-  g->nt = p->nt;
-  g->rot_seed = rot_seed;
-  g->tensor_mask = tensor_keyed ? -1 : 0;
-  g->logd = logd;
-  return OMF_OK;
-}
-
-unsigned grid_blocks(const omf_plan* p) { return (unsigned)(p->n_flat * (kSub / kBlk)); }
-
 int encode_max(omf_plan* p, const float* x, float alpha, int32_t s, int64_t d, const float* u, uint64_t seed,
                uint64_t offset, const float* bnorm_in, void* q, float* bnorm_out, bool rotate, uint32_t rot_seed,
                int32_t tensor_keyed, bool norm_only, void* stream) {
@@ -361,12 +244,12 @@ int encode_max(omf_plan* p, const float* x, float alpha, int32_t s, int64_t d, c
   DeviceGuard dg(p->device);
   if (!dg.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   RotGeom g;
-  if (int r = geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
+  if (int r = rot_geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
   const hipStream_t st = (hipStream_t)stream;
   EncArgs a = enc_args(p, EncCall{x, alpha, s, u, seed, offset, bnorm_in, norm_only ? nullptr : q, bnorm_out, norm_only,
                                   st, 0.0f, nullptr, 0u, nullptr, width});
   with_logd(logd, [&](auto L) {
-    launch_kernel(encode_kernel<L()>(width == 4, u != nullptr, rotate), dim3(grid_blocks(p)), dim3(kThreads), 0, st, a, g);
+    launch_kernel(encode_kernel<L()>(width == 4, u != nullptr, rotate), dim3(rot_grid_blocks(p)), dim3(kThreads), 0, st, a, g);
   });
   OMF_HIP(hipGetLastError());
   if (!norm_only) p->last_encoder = rotate ? kEncBucketedMaxRot : kEncBucketedMax;
@@ -386,10 +269,10 @@ int rotate_bucketed(omf_plan* p, const float* x, int64_t d, uint32_t rot_seed, i
   DeviceGuard dg(p->device);
   if (!dg.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   RotGeom g;
-  if (int r = geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
+  if (int r = rot_geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
   const int inv = inverse != 0;
   with_logd(logd, [&](auto L) {
-    hipLaunchKernelGGL((qsgd_bucket_rotate<L()>), dim3(grid_blocks(p)), dim3(kThreads), 0, (hipStream_t)stream, x, y, g, inv);
+    hipLaunchKernelGGL((qsgd_bucket_rotate<L()>), dim3(rot_grid_blocks(p)), dim3(kThreads), 0, (hipStream_t)stream, x, y, g, inv);
   });
   OMF_HIP(hipGetLastError());
   return OMF_OK;
@@ -405,7 +288,7 @@ int sum_rot(omf_plan* p, const void* const* q, const float* const* bnorm, int32_
   DeviceGuard dg(p->device);
   if (!dg.ok) return fail(OMF_EHIP, "hipSetDevice failed");
   RotGeom g;
-  if (int r = geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
+  if (int r = rot_geom(p, logd, rot_seed, tensor_keyed, &g)) return r;
   const LevelScale lv(levels);
   SumCallBase c;
   c.y = y; c.st = (hipStream_t)stream; c.levels = lv.levels; c.inv_levels = lv.inv_levels;
@@ -424,7 +307,7 @@ int sum_rot(omf_plan* p, const void* const* q, const float* const* bnorm, int32_
       BSumArgs<N()> a{};
       for (int k = 0; k < N(); ++k) a.q[k] = q[k0 + k];
       sum_common_args(a, c, N());
-      auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid_blocks(p)), dim3(kThreads), 0, c.st, a, g, r); };
+      auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(rot_grid_blocks(p)), dim3(kThreads), 0, c.st, a, g, r); };
       if (width == 8) {
         if (lv.pow2) go(qsgd_bucket_decode_sum_rot<1, true, N()>); else go(qsgd_bucket_decode_sum_rot<1, false, N()>);
       } else {

@@ -508,7 +508,8 @@ class DeviceAggregator:
 
         self._check_fresh()
         layers = list(layers)
-        if self._bucketed_step_serves(compressor, self.total_samples + int(number_samples)):
+        if (self._bucketed_step_serves(compressor, self.total_samples + int(number_samples))
+                or self._bucketed_max_step_serves(compressor, self.total_samples + int(number_samples))):
             return self.sum_apply_encode([(layers, number_samples)], compressor, keep_sum=keep_sum)
         last: Dict[str, object] = {}
         for L in layers:
@@ -575,6 +576,45 @@ class DeviceAggregator:
                 and 0 <= compressor.s <= 30 and float(total) != 0.0 and bool(self.names)
                 and all(numel(self.shapes[n]) > 0 for n in self.names))
 
+    # The max-scaled step (omf_ps_sum_encode_bucketed_max) is the default: measured ahead of the sequence it replaces
+    # by more than the round spreads in every cell of both rotation settings; False routes those
+    # rounds through that sequence again.  requantise_rotated takes the rotated downlink from the clients' sum in
+    # the rotated domain (no forward transform): other downlink bytes, so it is opt-in, and it needs a fresh
+    # accumulator (otherwise the exact form runs).
+    fuse_bucketed_max_step = True
+    requantise_rotated = False
+
+    def _bucketed_max_step_serves(self, compressor, total) -> bool:
+        """``_bucketed_step_serves`` for ``bucket_norm="max"`` compressors (never packed), rotating or not."""
+        from .hybrid.compression.qsgd import QSGDQuantCompression
+        return (self.fuse_bucketed_max_step and isinstance(compressor, QSGDQuantCompression)
+                and compressor.bucket_size is not None and compressor.rng == "philox" and self.compute_mean
+                and compressor.bucket_norm == "max"
+                and 0 <= compressor.s <= 30 and float(total) != 0.0 and bool(self.names)
+                and all(numel(self.shapes[n]) > 0 for n in self.names))
+
+    def _bucketed_max_step(self, run, total, compressor, keep_sum: bool, fresh: bool):
+        """``_bucketed_step`` for a max-scaled compressor (``Plan.ps_sum_encode_bucketed_max``): ``run`` is a
+        non-empty run of staged updates of the compressor's own bucket size and rotation.  ``fresh``: nothing has
+        been added to the accumulator, so ``requantise_rotated`` may drop it."""
+        from .hybrid.communicator.global_grpc_compression import (_encode_dense_layer, _host_memory_policy,
+                                                                  qsgd_bucketed_layers_from_arena)
+        _host_memory_policy()
+        if self.avg is None:
+            self.avg = torch.empty_like(self.acc)
+        d, s, seed = compressor.bucket_size, compressor.s, compressor.wire_rotation_seed
+        _, width, level, _, _ = run[0]
+        req = bool(self.requantise_rotated and compressor.rotate and fresh)
+        _, q, bn = self.plan.ps_sum_encode_bucketed_max(
+            None if req else self.acc, [a[0] for a in run], [a[3] for a in run], width, level, d, float(total), s,
+            rotate=compressor.rotate, rotation_seed=seed or 0, tensor_keyed=False, requantise_rotated=req,
+            sum_out=self.acc if keep_sum else None, avg_out=self.avg, seed=compressor.philox_key(),
+            offset=compressor._next_call())
+        avg = {n: self._avg_slice(n).view(self.shapes[n]) for n in self.names}
+        got = qsgd_bucketed_layers_from_arena(self.plan, q, bn, self.names, [self.shapes[n] for n in self.names], 2**s,
+                                              d, rotation_seed=seed)
+        return avg, [L if L is not None else _encode_dense_layer(n, avg[n]) for n, L in zip(self.names, got)]
+
     def _bucketed_step(self, run, total, compressor, keep_sum: bool):
         """``acc + Σ decode(run)``, its average over ``total`` and the average's bucketed downlink in one call
         (``Plan.ps_sum_encode_bucketed``).  ``run``: staged ``q_args`` of like bucketed updates, possibly none (the
@@ -604,13 +644,16 @@ class DeviceAggregator:
         every update is staged first, all but the trailing run of like bucketed updates (QSGD-only, one wire,
         width, level and bucket size; at most ``max_batch``) are applied as ``accumulate_many`` applies them, and
         the trailing run is summed onto the accumulator, averaged and re-encoded by ``_bucketed_step`` — the
-        average is never re-read.  ``keep_sum`` as in ``accumulate_apply_encode``.  Same bytes, counters and
+        average is never re-read.  A ``bucket_norm="max"`` compressor takes ``_bucketed_max_step`` instead, over a trailing
+        run of updates of its own bucket size and rotation (``fuse_bucketed_max_step``).  ``keep_sum`` as in
+        ``accumulate_apply_encode``.  Same bytes, counters and
         return as the two calls; anything that cannot fuse (another compressor, a trailing update with Top-K or
         dense layers, a zero total) takes them.  If staging update j raises, the updates before it are applied
         and counted, then the exception propagates, as in ``accumulate_many``."""
         self._check_fresh()
         updates = list(updates)
-        if not self._bucketed_step_serves(compressor, 1):
+        as_max = self._bucketed_max_step_serves(compressor, 1)
+        if not as_max and not self._bucketed_step_serves(compressor, 1):
             self.accumulate_many(updates, max_batch)
             return self.apply_and_encode(compressor)
         staged: List[tuple] = []
@@ -621,20 +664,31 @@ class DeviceAggregator:
             self._apply_many(staged, max_batch)
             raise
 
+        if as_max:  # one bucket size and rotation for both directions
+            like = (("bucket_rot", compressor.bucket_size, compressor.rotation_seed) if compressor.rotate
+                    else ("bucket", compressor.bucket_size))
+
         def bucketed_only(st):
-            return (st[0] is not None and st[1] is None and not st[2] and isinstance(st[0][4], tuple)
-                    and st[0][4][0] != "bucket_rot")  # the fused step sums in the unrotated domain
+            if not (st[0] is not None and st[1] is None and not st[2] and isinstance(st[0][4], tuple)):
+                return False
+            if as_max:
+                return st[0][4] == like
+            return st[0][4][0] != "bucket_rot"  # the L2 step sums in the unrotated domain
 
         tail = len(staged)
         while (tail > 0 and len(staged) - tail < max(int(max_batch), 1) and bucketed_only(staged[tail - 1][0])
                and staged[tail - 1][0][0][1:3] == staged[-1][0][0][1:3] and staged[tail - 1][0][0][4] == staged[-1][0][0][4]):
             tail -= 1
         total = self.total_samples + sum(int(ns) for _, ns in staged)
-        if tail == len(staged) or not self._bucketed_step_serves(compressor, total):
+        serves = self._bucketed_max_step_serves if as_max else self._bucketed_step_serves
+        if tail == len(staged) or not serves(compressor, total):
             self._apply_many(staged, max_batch)
             return self.apply_and_encode(compressor)
+        fresh = self.update_count == 0 and tail == 0
         self._apply_many(staged[:tail], max_batch)
-        out = self._bucketed_step([st[0] for st, _ in staged[tail:]], total, compressor, keep_sum)
+        run = [st[0] for st, _ in staged[tail:]]
+        out = (self._bucketed_max_step(run, total, compressor, keep_sum, fresh) if as_max
+               else self._bucketed_step(run, total, compressor, keep_sum))
         self.update_count += len(staged) - tail
         self.total_samples = total
         if not keep_sum:
